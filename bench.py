@@ -2,9 +2,15 @@
 """Headline benchmark (BASELINE.json): events/sec (node) + p50 alert latency, 1M-key tumbling
 event-time window, keyBy all-to-all, at 1/2/4/8 MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs: set-up, W warm-up steps, K timed steps, the
+outputs as of the last timed step with --dump-outputs, one JSON line. --full adds the untimed
+figures reported next to the headline: the alert-latency phase (further steps until
+--latency-firings firings), the same job on hashed keyed state and, at G > 1, with the
+per-event records exchange.
 
 Each rank = one GPU = one source partition + one shard of the keyed window state. W untimed
 steps, then exactly K timed steps bracketed by barrier + device sync; the slowest rank's time is
@@ -30,6 +36,85 @@ from mxstream.parallel.comm import init_distributed  # noqa: E402
 
 METRIC = "events/sec (node) + p50 alert latency, 1M-key tumbling window at 1/2/4/8 MI355X"
 
+DUMP_EVENT_ROWS = 1 << 20   # --dump-outputs: sampled events of the last step (3 columns)
+DUMP_FIRED_ROWS = 1 << 18   # --dump-outputs: rows kept of one set of fired windows (4 columns)
+DUMP_SEED = 20190828
+
+
+class RecordingBench(TumblingWindowBench):
+    """--dump-outputs: keeps the alerts of the run's latest firing, by reference and one firing
+    only. Fired rows are views of the operator's pinned host slab: rows still held when the next
+    window fires make that firing allocate a new slab inside the timed region (measured: 5 ms,
+    against 0.28 ms for a step), and copying them costs about as much as a step. Tumbling windows
+    of `window_ms` over steps of `step_span_ms` fire once every `period` steps, so exactly one
+    firing is triggered by the run's last `period` steps: that one is kept, nothing before it."""
+
+    def __init__(self, cfg, comm, device, total_steps: int):
+        super().__init__(cfg, comm, device)
+        period = -(-cfg.window_ms // cfg.step_span_ms)
+        self.keep_from_seq = max(1, total_steps - period + 1)  # FireResult.seq is 1-based
+        self.kept: list = []
+
+    def _account(self, fired) -> int:
+        if fired:
+            keep = [r for r in fired if r.seq >= self.keep_from_seq]
+            if keep:
+                self.kept = keep
+        return super()._account(fired)
+
+    def latest_alerts(self) -> list:
+        """(window start, end, batch seq, keys, values, raw, counts) of the kept firing."""
+        self.keep_from_seq = 1 << 62  # steps after the dump keep nothing
+        return [(r.window_start, r.window_end, r.seq, r.keys, r.values, r.raw, r.counts)
+                for r in self.kept]
+
+
+def _sample(n: int, rows: int):
+    """Fixed, seeded choice of `rows` of n row numbers in ascending order (all when n <= rows)."""
+    import numpy as np
+
+    if n <= rows:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=rows, replace=False))
+
+
+def dump_outputs(path: str, bench: RecordingBench, rank: int, world: int, totals: dict) -> None:
+    """What the timed path has handed its caller when its last step ends, as float64 .npy files
+    (under 64 MB in all): the latest alerts (`alerts_*`: keys, mapped values, raw sums, counts,
+    and per fired window its start, end, triggering batch and row count), a seeded sample of the
+    events the last step ingested (`events_*`) and the run's counters (`totals`). Only a step
+    whose watermark closes a window returns alerts (1-min windows, 5 s steps: every 12th), so
+    the alerts are those of the latest such step, the last timed step or one before it; a run
+    too short to close a window writes no `alerts_*`. Rows are ordered by window, then key: the
+    fire kernel's own row order is not fixed."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if world == 1 else f".rank{rank}"
+
+    def save(name: str, arr) -> None:
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+    fired = sorted(bench.latest_alerts(), key=lambda r: r[:3])
+    cols = {"keys": [], "values": [], "raw": [], "counts": []}
+    for _start, _end, _seq, keys, *rest in fired:
+        order = np.argsort(keys, kind="stable")
+        for name, col in zip(cols, (keys, *rest)):
+            # raw / counts: None where the operator emits key + value only
+            cols[name].append((np.zeros(len(order)) if col is None else col)[order].astype(np.float64))
+    rows = sum(len(c) for c in cols["keys"])
+    if rows:
+        keep = _sample(rows, DUMP_FIRED_ROWS)
+        save("alerts_windows", np.array([[s, e, seq, len(k)] for s, e, seq, k, *_ in fired]))
+        for name, parts in cols.items():
+            save(f"alerts_{name}", np.concatenate(parts)[keep])
+    idx = torch.from_numpy(_sample(bench.cfg.batch, DUMP_EVENT_ROWS)).to(bench.device)
+    for name, col in (("keys", bench.keys), ("ts", bench.ts), ("vals", bench.vals)):
+        save(f"events_{name}", col.index_select(0, idx).cpu().numpy())
+    save("totals", np.array(list(totals.values()), dtype=np.float64))
+    with open(os.path.join(path, f"totals{suffix}.names.json"), "w") as f:
+        json.dump(list(totals), f)
+
 
 def main() -> int:
     ap = argparse.ArgumentParser()
@@ -52,11 +137,19 @@ def main() -> int:
                     help="write a Chrome trace of the timed steps (stage spans; roctx with MXS_ROCTX=1)")
     ap.add_argument("--step-timeout-ms", type=int, default=0,
                     help="watchdog: abort the run if one step makes no progress for this long")
-    ap.add_argument("--latency-firings", type=int, default=12,
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is reported next to the headline: the alert-latency "
+                         "phase, the hashed-key run and (G > 1) the records-exchange run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write the latest alerts the timed path has "
+                         "returned when its last step ends (and a seeded sample of the events "
+                         "that step ingested) as DIR/<name>.npy")
+    ap.add_argument("--latency-firings", type=int, default=None,
                     help="after the timed steps: run untimed steps until this many firings "
-                         "for the p50/p99 alert latency (0: timed firings only)")
+                         "for the p50/p99 alert latency (0: timed firings only; default 12 "
+                         "with --full, else 0)")
     ap.add_argument("--no-hashed-figure", action="store_true",
-                    help="skip the untimed-in-headline hashed-key run reported next to it")
+                    help="--full: skip the untimed-in-headline hashed-key run reported next to it")
     ap.add_argument("--exchange", choices=["auto", "partials", "records"], default="auto",
                     help="G > 1 keyBy strategy of the headline: partials = local-global "
                          "aggregation (partial accumulators cross one all-to-all per fired "
@@ -67,8 +160,10 @@ def main() -> int:
                          "for this long, so its clocks are at their sustained level when the "
                          "warm-up steps start (reported in the JSON)")
     ap.add_argument("--no-records-figure", action="store_true",
-                    help="G > 1: skip the per-event-exchange (records) run reported next to it")
+                    help="--full, G > 1: skip the per-event-exchange (records) run reported next to it")
     a = ap.parse_args()
+    if a.latency_firings is None:
+        a.latency_firings = 12 if a.full else 0
     faulthandler.enable()  # an abort or fault prints every thread's Python stack to stderr
 
     if os.environ.get("MXS_SPIN") == "1" and a.device == "cuda":
@@ -96,7 +191,8 @@ def main() -> int:
                               dense_keys=not a.hashed_keys and not records, key32=a.int32_keys,
                               zipf=a.zipf, pipeline=False if a.no_pipeline else None,
                               exchange=a.exchange)
-    bench = TumblingWindowBench(cfg, comm, device)
+    bench = (RecordingBench(cfg, comm, device, a.warmup + a.steps) if a.dump_outputs
+             else TumblingWindowBench(cfg, comm, device))
     if a.trace:
         from mxstream.utils import trace
         from mxstream.utils.metrics import StageTimer
@@ -175,11 +271,17 @@ def main() -> int:
     op_metrics = bench.op.metrics
     op_info = {"local_global": bench.op.local_global, "dense": bool(bench.op.dense_bits),
                "rec_w": bench.op.rec_w}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, bench, comm.rank, comm.world, {
+            "alerts": bench.alerts - alerts0, "steps": a.steps, "warmup": a.warmup,
+            "late_dropped": op_metrics.num_late_records_dropped,
+            "records_in": op_metrics.num_records_in, "fires": op_metrics.num_fires})
 
     # ---- after the timed region (not part of `value`) ----
     # Latency phase: the timed steps cover few firings (5 s of event time per step, 1-min
     # windows: one firing per 12 steps), so the alert-latency quantiles come from further,
-    # untimed steps until `--latency-firings` firings were observed.
+    # untimed steps until `--latency-firings` firings were observed (--full; a plain run
+    # reports the quantiles over the firings of its timed steps and runs no further step).
     timed_firings = len(bench.latencies_ms)
     lat_steps = 0
     # Every rank runs the same number of extra steps (they are collective): the stop decision
@@ -222,7 +324,7 @@ def main() -> int:
         return a.batch * a.steps * comm.world / float(tt.item()), float(tt.item()) / a.steps * 1e3
 
     hashed = None
-    if not a.no_hashed_figure and not a.hashed_keys and not records:
+    if a.full and not a.no_hashed_figure and not a.hashed_keys and not records:
         del bench
         ev_s, ms = side_run(TumblingBenchConfig(keys=a.keys, batch=a.batch, cap_log2=a.cap_log2,
                                                 dense_keys=False, zipf=a.zipf,
@@ -232,7 +334,7 @@ def main() -> int:
     # G > 1 and a partials headline: the per-event keyBy shuffle (BASELINE config 3's
     # "all-to-all") measured the same way, reported next to it (not the headline value).
     recfig = None
-    if comm.world > 1 and not records and not a.no_records_figure:
+    if a.full and comm.world > 1 and not records and not a.no_records_figure:
         ev_s, ms = side_run(TumblingBenchConfig(keys=a.keys, batch=a.batch, cap_log2=a.cap_log2,
                                                 dense_keys=False, zipf=a.zipf,
                                                 pipeline=False if a.no_pipeline else None,
@@ -250,6 +352,7 @@ def main() -> int:
             "n_gpus": n,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": dt / a.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",

@@ -23,7 +23,7 @@ for step in "$@"; do
     t_*) f=${step#t_}; timeout -k 10 600 python -u -m pytest tests/test_$f.py -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider > "$out/pytest_$f.log" 2>&1
          st=$?; tail -3 "$out/pytest_$f.log"; [ $st -eq 0 ] || exit $st ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || exit $? ;;
-    bench) timeout -k 10 300 python bench.py --steps 48 --warmup 8 > "$out/bench.log" 2>&1 || exit $? ;;
+    bench) timeout -k 10 300 python bench.py --full --steps 48 --warmup 8 >"$out/bench.log" 2>&1 || exit $? ;;
     bench_nopipe) timeout -k 10 300 python bench.py --steps 48 --warmup 8 --no-pipeline > "$out/bench_nopipe.log" 2>&1 || exit $? ;;
     bench_hashed) timeout -k 10 300 python bench.py --steps 48 --warmup 8 --hashed-keys > "$out/bench_hashed.log" 2>&1 || exit $? ;;
     prof_bench_hashed) prof bench_hashed python3 bench.py --steps 24 --warmup 6 --hashed-keys || exit $? ;;
@@ -43,7 +43,7 @@ for step in "$@"; do
     prof_zipf_*) z=${step#prof_zipf_}; prof "zipf_$z" python3 bench.py --steps 24 --warmup 6 --zipf "$z" || exit $? ;;
     cfg6z_*) z=${step#cfg6z_}; z=${z%_*}; m=${step##*_}; extra=""; [ "$m" = valu ] && extra=--valu; timeout -k 10 300 python -m mxstream.models.bench_configs --config 6 --steps 20 --warmup 5 --zipf "$z" $extra > "$out/$step.json" 2>&1 || exit $? ;;
     cfg5r) timeout -k 10 300 python -m mxstream.models.bench_configs --config 5 --steps 20 --warmup 14 --revisit 0.01 > "$out/cfg5r.json" 2>&1 || exit $? ;;
-    bench20) timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$out/bench20.log" 2>&1 || exit $? ;;
+    bench20) timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > "$out/bench20.log" 2>&1 || exit $? ;;
     cfg1) timeout -k 10 300 python -m mxstream.models.bench_configs --config 1 --steps 20 --warmup 3 > "$out/cfg1.json" 2>&1 || exit $? ;;
     cfg1t*) t=${step#cfg1t}; timeout -k 10 300 python -m mxstream.models.bench_configs --config 1 --threads $t --steps 20 --warmup 3 > "$out/cfg1_t$t.json" 2>&1 || exit $? ;;
     cfg1gpu) timeout -k 10 300 python -m mxstream.models.bench_configs --config 1 --gpu-parse --steps 20 --warmup 3 > "$out/cfg1_gpu.json" 2>&1 || exit $? ;;
