@@ -12,9 +12,17 @@
 //     C[32 segments x 32 metrics] = A[32 segments x 32 records] (one-hot: record k in segment r)
 //                                 * B[32 records x 32 metrics]  (the records' metric vectors)
 //
-// with v_mfma_f32_32x32x16_bf16 (2 k-steps). B is split into three bf16 terms (hi + mid + lo
-// reproduces every f32 exactly, A is exactly 0/1), so the three MFMAs per k-step accumulate in
-// f32 and the result equals an f32 segmented sum up to summation order. Only the populated rows
+// with v_mfma_f32_32x32x16_bf16 (2 k-steps). B is split into three bf16 terms and A is exactly
+// 0/1, so the three MFMAs per k-step accumulate in f32 and the result equals an f32 segmented sum
+// up to summation order. hi + mid + lo carries 24 significand bits, so it reproduces v exactly
+// for 2^-110 <= |v| < 0x1.FFp127 (bit pattern 0x7F7F8000); below about 2^-110 the low term
+// underflows bf16 (and split terms below 2^-126 are bf16 subnormals), so up to 3 * 2^-126 per
+// record may be lost. At and above 0x1.FFp127 (where bf16 rounding makes hi infinite), and for
+// +-Inf and NaN, one of the three terms is NaN, and NaN x 0 = NaN in the one-hot product spreads
+// that record's metric to every segment of its tile. Such a product shows as an all-NaN metric
+// column of C; a wave vote per tile and 32-metric block then discards it and sums the block with
+// the VALU walk (vtile_walk), which adds only a record's own values: every cell is the f32 sum
+// of its own records, non-finite where IEEE says so. Only the populated rows
 // of C (one per run, ~3 per tile at 16 events/key/step) are flushed to HBM, with 128-byte
 // contiguous no-return atomics (two 128-B row segments per wave instruction — the full-rate
 // atomic shape). Compared with per-record LDS/HBM atomics, hot keys (long runs) never serialise
@@ -96,6 +104,9 @@ __device__ __forceinline__ uint32_t vblock_scan(uint32_t v, uint32_t* wsum) {
   return wsum[wid] + x - v;
 }
 
+// v = hi + mid + lo. NaN: hi is NaN. +-Inf: r1 = Inf - Inf, mid is NaN. Finite |v| >= 0x1.FFp127:
+// hi = +-Inf, r1 = mid = -+Inf, lo = Inf - Inf is NaN. The non-finite guard of the MFMA path
+// relies on this NaN term.
 __device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
   hi = (__bf16)v;
   const float r1 = v - (float)hi;
@@ -123,6 +134,39 @@ __device__ __forceinline__ size_t vslot_index(uint32_t cc, const VecAggPlan& p, 
                                               size_t nslots, size_t sbase, uint32_t mask) {
   const int64_t pane = p.pane_base + q0 + (cc >> p.cap_log2);
   return (size_t)(pane & (p.ring - 1)) * nslots + sbase + (cc & mask);
+}
+
+// VALU segmented sum of metric block n (metrics 32n .. 32n+31) of one sorted 32-record tile:
+// half-wave h walks records 16h .. 16h+15 of the tile in order, lane r holds metric r of the
+// current run and flushes it when the run ends. Plain f32 adds of the record's own values: a
+// non-finite metric stays in its own cell. Whole body of mode 1, and mode 0's path for tile
+// blocks that hold a value the bf16 split cannot carry.
+__device__ __forceinline__ void vtile_walk(const VecAggPlan& p, const float* __restrict__ vec,
+                                           float* __restrict__ acc_g, const uint32_t* srow,
+                                           const uint32_t* segrow, int segid, uint32_t base,
+                                           uint32_t nrec, int n, int r, int h, int64_t q0,
+                                           size_t nslots, size_t sbase, uint32_t mask) {
+  const int D = p.dim;
+  float sum = 0.0f;
+  int cur = -1;
+  for (int j = 0; j < 16; ++j) {
+    const uint32_t k = base + 16 * h + j;
+    const int sk = __shfl(segid, 16 * h + j);
+    if (k >= nrec) break;
+    if (sk != cur) {
+      if (cur >= 0) {
+        const size_t gi = vslot_index(segrow[cur], p, q0, nslots, sbase, mask);
+        atomicAdd(&acc_g[gi * D + 32 * n + r], sum);
+      }
+      cur = sk;
+      sum = 0.0f;
+    }
+    sum += vec[(size_t)srow[k] * D + 32 * n + r];
+  }
+  if (cur >= 0) {
+    const size_t gi = vslot_index(segrow[cur], p, q0, nslots, sbase, mask);
+    atomicAdd(&acc_g[gi * D + 32 * n + r], sum);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -288,6 +332,15 @@ __global__ __launch_bounds__(kVThreads) void vec_window_agg_kernel(
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bm, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bh, acc, 0, 0, 0);
               }
+              // A value the split cannot carry (NaN, +-Inf, |v| >= 0x1.FFp127) has a NaN among
+              // its three terms (split3), and NaN x 0 = NaN x 1 = NaN: all 32 rows of its metric
+              // column of C are NaN, also the rows of other keys' segments. Row 4h of each column
+              // tells; one wave vote drops the product and sums this block with the walk.
+              if (__any(acc[0] != acc[0])) {
+                vtile_walk(p, vec, acc_g, srow, segtab + wid * 32, segid, base, nrec, n, r, h, q0,
+                           nslots, sbase, mask);
+                continue;
+              }
               // C/D map of 32x32: col = lane & 31 (metric), row = (i&3) + 8*(i>>2) + 4*h (segment).
 #pragma unroll
               for (int i = 0; i < 16; ++i) {
@@ -299,30 +352,10 @@ __global__ __launch_bounds__(kVThreads) void vec_window_agg_kernel(
               }
             }
           } else {
-            // VALU variant: half-wave h walks records 16h .. 16h+15 of the tile in order, lane r
-            // holds metric r of the current run and flushes it when the run ends.
-            for (int n = 0; n < (D >> 5); ++n) {
-              float sum = 0.0f;
-              int cur = -1;
-              for (int j = 0; j < 16; ++j) {
-                const uint32_t k = base + 16 * h + j;
-                const int sk = __shfl(segid, 16 * h + j);
-                if (k >= nrec) break;
-                if (sk != cur) {
-                  if (cur >= 0) {
-                    const size_t gi = vslot_index(segtab[wid * 32 + cur], p, q0, nslots, sbase, mask);
-                    atomicAdd(&acc_g[gi * D + 32 * n + r], sum);
-                  }
-                  cur = sk;
-                  sum = 0.0f;
-                }
-                sum += vec[(size_t)srow[k] * D + 32 * n + r];
-              }
-              if (cur >= 0) {
-                const size_t gi = vslot_index(segtab[wid * 32 + cur], p, q0, nslots, sbase, mask);
-                atomicAdd(&acc_g[gi * D + 32 * n + r], sum);
-              }
-            }
+            // VALU variant: every block of every tile takes the walk.
+            for (int n = 0; n < (D >> 5); ++n)
+              vtile_walk(p, vec, acc_g, srow, segtab + wid * 32, segid, base, nrec, n, r, h, q0,
+                         nslots, sbase, mask);
           }
           __builtin_amdgcn_wave_barrier();
         }

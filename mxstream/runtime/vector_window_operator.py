@@ -11,7 +11,10 @@ Everything except the accumulator is the scalar operator (``KeyedWindowOperator`
 keyBy partition (records carry the event's row as their value), watermark valve, pane ring,
 firing schedule, lateness re-firing and purge. The aggregation kernel (csrc/vector_hip.hip)
 counting-sorts each sub-table's records by (pane, slot) in LDS and reduces every 32-record tile
-as one-hot x vectors on ``v_mfma_f32_32x32x16_bf16`` (3-term bf16 split = exact f32 inputs).
+as one-hot x vectors on ``v_mfma_f32_32x32x16_bf16``. The 3-term bf16 split carries an f32 input
+exactly for 2^-110 <= |v| < 0x1.FFp127 (smaller values lose at most 3 * 2^-126 each). A tile block
+that holds NaN, +-Inf or a larger finite value is summed on the VALU instead, so such a metric
+gives the IEEE f32 sum in its own (key, pane) cell and never reaches another key's.
 With G > 1 the vectors travel next to their records in the all-to-all (gather into the send
 layout, then positional reads on the receiver).
 """
@@ -94,9 +97,13 @@ class VectorWindowOperator(KeyedWindowOperator):
                 "vec": np.zeros(0, vdt), "cnt": np.zeros(0, np.int32),
                 "dirty": np.zeros(0, np.uint8)}
         kg = np.zeros(0, np.int32)
-        if self.min_live_pane is not None and live.numel():
-            panes = torch.arange(self.min_live_pane, self.max_seen_pane + 1, device=self.device)
-            idx = ((panes & (self.ring - 1)) * self.nslots)[:, None] + live[None, :]
+        # Pane range and ring as of the freeze for a frozen copy: the properties go to the live
+        # native step, which keeps moving while the export runs on its worker thread.
+        book = self._book()
+        lo, hi, ring = book["min_live_pane"], book["max_seen_pane"], book["ring"]
+        if lo is not None and live.numel():
+            panes = torch.arange(lo, hi + 1, device=self.device)
+            idx = ((panes & (ring - 1)) * self.nslots)[:, None] + live[None, :]
             cnt = self.cnt_g[idx]
             sel = cnt > 0
             flat = idx[sel]
@@ -109,7 +116,6 @@ class VectorWindowOperator(KeyedWindowOperator):
                     "vec": np.ascontiguousarray(vec).view(vdt).reshape(-1),
                     "cnt": cnt[sel].cpu().numpy(),
                     "dirty": self.dirty_g[flat].cpu().numpy()}
-        book = self._book()
         meta = {"kind": "vector_window", "size": self.size, "slide": self.slide,
                 "offset": self.offset, "lateness": self.lateness, "dim": self.dim,
                 "avg": self.avg, "time_mode": self.time_mode, "wm": book["wm"],
