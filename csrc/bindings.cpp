@@ -981,6 +981,33 @@ PYBIND11_MODULE(_mxs_native, m) {
     py::gil_scoped_release nogil;
     cpu::segment_median_select(P<int64_t>(heads), nseg, total, P<uint64_t>(ord), P<double>(out));
   });
+  // Quantiles in parts per million (1..8 of them); out is [len(ppm)][nseg] doubles.
+  auto quantile_spec = [](const std::vector<int64_t>& ppm) {
+    if (ppm.empty() || ppm.size() > (size_t)kMaxQuantiles)
+      throw std::invalid_argument("segment_quantile_select: 1..8 quantiles");
+    QuantileSpec qs{};
+    qs.q = (int)ppm.size();
+    for (size_t j = 0; j < ppm.size(); ++j) {
+      if (ppm[j] < 0 || ppm[j] > (int64_t)kPpmOne)
+        throw std::invalid_argument("segment_quantile_select: ppm outside 0..1000000");
+      qs.ppm[j] = (uint32_t)ppm[j];
+    }
+    return qs;
+  };
+  m.def("gpu_segment_quantile_select", [quantile_spec](intptr_t heads, int64_t nseg, int64_t total,
+                                                       intptr_t ord, std::vector<int64_t> ppm,
+                                                       intptr_t out, intptr_t stream) {
+    gpu::segment_quantile_select(P<int64_t>(heads), nseg, total, P<uint64_t>(ord),
+                                 quantile_spec(ppm), P<double>(out), stream);
+  });
+  m.def("cpu_segment_quantile_select", [quantile_spec](intptr_t heads, int64_t nseg, int64_t total,
+                                                       intptr_t ord, std::vector<int64_t> ppm,
+                                                       intptr_t out) {
+    const QuantileSpec qs = quantile_spec(ppm);
+    py::gil_scoped_release nogil;
+    cpu::segment_quantile_select(P<int64_t>(heads), nseg, total, P<uint64_t>(ord), qs,
+                                 P<double>(out));
+  });
   m.def("gpu_segment_median", [](intptr_t heads, int64_t nseg, int64_t total, intptr_t ord,
                                  intptr_t out, intptr_t stream) {
     gpu::segment_median(P<int64_t>(heads), nseg, total, P<uint64_t>(ord), P<double>(out), stream);

@@ -561,6 +561,35 @@ void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total,
   }
 }
 
+void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
+                             const uint64_t* ord, const QuantileSpec& qs, double* out) {
+  if (qs.q < 1 || qs.q > kMaxQuantiles)
+    throw std::invalid_argument("segment_quantile_select: 1..8 quantiles");
+  for (int j = 0; j < qs.q; ++j)
+    if (qs.ppm[j] > kPpmOne) throw std::invalid_argument("segment_quantile_select: ppm > 1e6");
+  std::vector<uint64_t> v;
+  for (int64_t sg = 0; sg < nseg; ++sg) {
+    const int64_t a = heads[sg], e = sg + 1 < nseg ? heads[sg + 1] : total, n = e - a;
+    if (n <= 0) {
+      for (int j = 0; j < qs.q; ++j) out[(int64_t)j * nseg + sg] = 0.0;
+      continue;
+    }
+    // One nth_element per distinct rank: an equal rank of an earlier column is copied.
+    v.assign(ord + a, ord + e);
+    for (int j = 0; j < qs.q; ++j) {
+      const int64_t r = quantile_rank(n, qs.ppm[j]);
+      int prev = 0;
+      while (prev < j && quantile_rank(n, qs.ppm[prev]) != r) ++prev;
+      if (prev < j) {
+        out[(int64_t)j * nseg + sg] = out[(int64_t)prev * nseg + sg];
+        continue;
+      }
+      std::nth_element(v.begin(), v.begin() + r, v.end());
+      out[(int64_t)j * nseg + sg] = as_f64(f64_from_order_bits(v[r]));
+    }
+  }
+}
+
 void segment_median(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
                     double* out) {
   for (int64_t s = 0; s < nseg; ++s) {

@@ -4256,6 +4256,59 @@ __global__ __launch_bounds__(256) void segment_median_select_kernel(
   }
 }
 
+// qs.q nearest-rank quantiles (mxs_common.h quantile_rank) of every segment of unsorted order
+// bits; out[j * nseg + s] is the element itself, no interpolation. The median kernel's layout
+// (one wave per segment, kMedLds values of LDS per wave): a short segment is staged in LDS once
+// and every rank is selected from that copy, a longer one selects over global memory. Quantiles
+// that fall on one rank (always some for small n) cost one select and are written to every
+// column that asked for the rank.
+__global__ __launch_bounds__(256) void segment_quantile_select_kernel(
+    const int64_t* __restrict__ heads, int64_t nseg, int64_t total, const uint64_t* __restrict__ ord,
+    QuantileSpec qs, double* __restrict__ out) {
+  __shared__ uint64_t buf[4][kMedLds];
+  __shared__ uint32_t hbuf[4][256];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  uint64_t* b = buf[w];
+  for (int64_t s = (int64_t)blockIdx.x * 4 + w; s < nseg; s += (int64_t)gridDim.x * 4) {
+    const int64_t a = heads[s], e = s + 1 < nseg ? heads[s + 1] : total;
+    const int64_t n = e - a;
+    if (n <= 0) {
+      if (lane < qs.q) out[(int64_t)lane * nseg + s] = 0.0;
+      continue;
+    }
+    const uint64_t* v = ord + a;
+    uint32_t* hist = reinterpret_cast<uint32_t*>(b);
+    if (n <= kMedLds) {
+      for (int i = lane; i < n; i += 64) b[i] = ord[a + i];
+      wave_lds_sync();
+      v = b;
+      hist = hbuf[w];
+    }
+    // Ranks live in registers (no indexed private array): rk[j] = -1 past q, so it never
+    // matches a selected rank. `pending` = the columns not written yet; all of it is uniform
+    // over the wave.
+    int64_t rk[kMaxQuantiles];
+#pragma unroll
+    for (int j = 0; j < kMaxQuantiles; ++j) rk[j] = j < qs.q ? quantile_rank(n, qs.ppm[j]) : -1;
+    uint32_t pending = (1u << qs.q) - 1u;
+    while (pending) {
+      const int first = __ffs((int)pending) - 1;
+      int64_t r = rk[0];
+#pragma unroll
+      for (int j = 1; j < kMaxQuantiles; ++j) r = first == j ? rk[j] : r;
+      // (every select ends in wave_lds_sync: the histogram and the staged copy are free again)
+      const double x = as_f64(f64_from_order_bits(wave_radix_select(v, n, r, hist, lane)));
+#pragma unroll
+      for (int j = 0; j < kMaxQuantiles; ++j) {
+        if (rk[j] == r) {
+          if (lane == 0) out[(int64_t)j * nseg + s] = x;
+          pending &= ~(1u << j);
+        }
+      }
+    }
+  }
+}
+
 int grid_for(int64_t n, int block, int max_blocks) {
   int64_t g = (n + block - 1) / block;
   if (g < 1) g = 1;
@@ -5679,6 +5732,19 @@ void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total, co
   if (nseg <= 0) return;
   hipLaunchKernelGGL(segment_median_select_kernel, dim3(grid_for(nseg, 4, 16384)), dim3(256), 0,
                      (hipStream_t)stream, heads, nseg, total, ord, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
+                             const uint64_t* ord, const QuantileSpec& qs, double* out,
+                             intptr_t stream) {
+  if (qs.q < 1 || qs.q > kMaxQuantiles)
+    throw std::invalid_argument("segment_quantile_select: 1..8 quantiles");
+  for (int j = 0; j < qs.q; ++j)
+    if (qs.ppm[j] > kPpmOne) throw std::invalid_argument("segment_quantile_select: ppm > 1e6");
+  if (nseg <= 0) return;
+  hipLaunchKernelGGL(segment_quantile_select_kernel, dim3(grid_for(nseg, 4, 16384)), dim3(256), 0,
+                     (hipStream_t)stream, heads, nseg, total, ord, qs, out);
   HIP_CHECK(hipGetLastError());
 }
 

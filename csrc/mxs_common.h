@@ -784,4 +784,19 @@ MXS_HD uint64_t f64_from_order_bits(uint64_t o) {
   return (o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFull) : ~o;
 }
 
+// Quantiles of a list window (segment_quantile_select): up to kMaxQuantiles per firing, each in
+// parts per million (the API rounds q in [0, 1] once; nothing below it touches floating point).
+constexpr int kMaxQuantiles = 8;
+constexpr uint32_t kPpmOne = 1000000u;
+struct QuantileSpec {
+  int q;
+  uint32_t ppm[kMaxQuantiles];
+};
+// Nearest rank: index into the n >= 1 ascending values of the element that is quantile `ppm`
+// (ceil(n * ppm / 1e6) - 1, clamped: ppm 0 = the minimum, 1e6 = the maximum).
+MXS_HD int64_t quantile_rank(int64_t n, uint32_t ppm) {
+  const int64_t idx = (n * (int64_t)ppm + (int64_t)(kPpmOne - 1)) / (int64_t)kPpmOne - 1;
+  return idx < 0 ? 0 : (idx > n - 1 ? n - 1 : idx);
+}
+
 }  // namespace mxs

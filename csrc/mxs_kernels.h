@@ -369,6 +369,11 @@ void segment_median(const int64_t* heads, int64_t nseg, int64_t total, const uin
 // The same medians over segments whose values are NOT sorted (selection per segment).
 void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total,
                            const uint64_t* ord, double* out, intptr_t stream);
+// qs.q nearest-rank quantiles (mxs_common.h quantile_rank) of the same unsorted segments:
+// out[j * nseg + s] = the element of segment s that is quantile qs.ppm[j] (0.0 when empty).
+void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
+                             const uint64_t* ord, const QuantileSpec& qs, double* out,
+                             intptr_t stream);
 void set_erase(uint64_t* set, uint32_t mask, const int64_t* keys, int64_t n, intptr_t stream);
 void set_insert_keys(uint64_t* set, uint32_t mask, const int64_t* keys, int64_t n,
                      intptr_t stream);
@@ -531,6 +536,8 @@ void segment_median(const int64_t* heads, int64_t nseg, int64_t total, const uin
                     double* out);
 void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total,
                            const uint64_t* ord, double* out);
+void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
+                             const uint64_t* ord, const QuantileSpec& qs, double* out);
 void scatter_partials(const uint64_t* keys, const uint64_t* acc, const uint32_t* cnt,
                       const uint32_t* n_in, const ScatPlan& plan, const int32_t* jhash,
                       const int32_t* kg_dest, uint32_t* cursor, Rec* out, uint32_t* flags);

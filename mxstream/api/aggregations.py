@@ -1,4 +1,5 @@
-"""Builtin AggregateFunctions that the planner can run natively.
+"""Builtin AggregateFunctions (and one ProcessWindowFunction, WindowQuantiles) that the planner
+can run natively.
 
 Each behaves exactly like the equivalent hand-written Flink AggregateFunction on the host path
 (e.g. ``AvgAggregate(1)`` is ComputeCpuAvg.java:31-58: accumulator (count, sum), result
@@ -6,7 +7,11 @@ Each behaves exactly like the equivalent hand-written Flink AggregateFunction on
 """
 from __future__ import annotations
 
-from .functions import AggregateFunction
+import struct
+
+from ..ops.kernels import MAX_QUANTILES, PPM_ONE
+from .functions import AggregateFunction, ProcessWindowFunction
+from .tuples import Tuple
 
 
 class BuiltinAggregate(AggregateFunction):
@@ -152,3 +157,50 @@ class VectorAvgAggregate(VectorSumAggregate):
     def get_result(self, acc):
         n, s = acc
         return [] if s is None else [v / n for v in s]
+
+
+def _double_order(x: float) -> int:
+    """Sort key of a double in Java ``Double.compare`` order (-0.0 < 0.0, NaN last): the order
+    bits of csrc/mxs_common.h f64_order_bits."""
+    if x != x:
+        return (1 << 64) - 1
+    b = struct.unpack("<Q", struct.pack("<d", x))[0]
+    return b ^ ((1 << 64) - 1) if b >> 63 else b | (1 << 63)
+
+
+def quantile_rank(n: int, ppm: int) -> int:
+    """Nearest rank: the index into n >= 1 ascending values of quantile `ppm` (parts per
+    million), ``clamp(ceil(n * ppm / 1e6) - 1, 0, n - 1)`` in integers."""
+    return min(max((n * ppm + PPM_ONE - 1) // PPM_ONE - 1, 0), n - 1)
+
+
+class WindowQuantiles(ProcessWindowFunction):
+    """Per key and window, the nearest-rank quantiles of one field: ``process`` emits one
+    ``Tuple(key, x_1, ..., x_Q)`` whose x_j is the window's element at sorted index
+    ``quantile_rank(n, ppm_j)`` -- the element itself, never an interpolation; 0.0 is the
+    minimum, 1.0 the maximum. 1 to 8 quantiles in [0, 1], duplicates and any order allowed.
+
+    Each quantile becomes an integer here, once: ``ppm = round(q * 1_000_000)``. ``native``
+    hands (field, ppm) to the planner, which runs tumbling and sliding event-time windows on
+    the device list-window operator (one staged copy of a key's values serves all Q ranks);
+    this method is the exact host implementation used otherwise."""
+
+    def __init__(self, field: int, quantiles):
+        qs = list(quantiles)
+        if not 1 <= len(qs) <= MAX_QUANTILES:
+            raise ValueError(f"WindowQuantiles takes 1 to {MAX_QUANTILES} quantiles, got {len(qs)}")
+        for q in qs:
+            if isinstance(q, bool) or not isinstance(q, (int, float)) or not 0 <= q <= 1:
+                raise ValueError(f"a quantile is a real number in [0, 1], got {q!r}")
+        self.field = field
+        self.ppm = tuple(int(round(q * PPM_ONE)) for q in qs)
+        self.native = ("quantiles", field, self.ppm)
+
+    def process(self, key, context, elements, out):
+        values = [t[self.field] for t in elements]
+        if all(isinstance(v, float) for v in values):
+            values.sort(key=_double_order)
+        else:
+            values.sort()
+        n = len(values)
+        out.collect(Tuple([key] + [values[quantile_rank(n, p)] if n else 0.0 for p in self.ppm]))

@@ -657,17 +657,25 @@ def config6(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_000
 
 
 def config8(steps: int, warmup: int, batch: int = 1 << 22, keys: int = 100_000,
-            device: str = "cuda") -> dict:
+            device: str = "cuda", quantiles=None) -> dict:
     """Process-window median at scale (ComputeCpuMiddle.java:34-48 shape): per host, the median
     CPU usage of every 1-min tumbling event-time window over `keys` hosts; every element is kept
     (ListState analogue, runtime/list_window_operator.py) and each firing sorts the window's
     values by host (one radix sort over the host-id bits) and selects each host's median
-    (segment_median_select: LDS bitonic sort / radix select per segment)."""
+    (segment_median_select: LDS bitonic sort / radix select per segment).
+    quantiles (e.g. [0.5, 0.95, 0.99]): the same window with WindowQuantiles' function instead
+    of the median -- Q nearest-rank quantiles per host from one firing."""
     from ..runtime.list_window_operator import KeyedListWindowOperator
 
     dev = torch.device(device)
     step_ms, disorder = 5_000, 1_000
-    op = KeyedListWindowOperator(size=60_000, device=dev)
+    if quantiles:
+        from ..api.aggregations import WindowQuantiles
+
+        ppm = WindowQuantiles(1, quantiles).ppm
+        op = KeyedListWindowOperator(size=60_000, device=dev, func=("quantiles", ppm))
+    else:
+        op = KeyedListWindowOperator(size=60_000, device=dev)
     kt = torch.empty(batch, dtype=torch.int64, device=dev)
     tt = torch.empty_like(kt)
     vt = torch.empty_like(kt)
@@ -700,11 +708,15 @@ def config8(steps: int, warmup: int, batch: int = 1 << 22, keys: int = 100_000,
         rows += step()
     _sync(dev)
     dt = time.perf_counter() - t0
-    return {"config": 8, "metric": "events/sec (process-window median per key, ListState)",
-            "value": batch * steps / dt, "unit": "events/s", "ms_per_step": dt / steps * 1e3,
-            "p50_fire_step_ms": statistics.median(lat) if lat else None, "medians": rows,
-            "keys": keys, "events_per_step": batch, "window_values": batch * 12,
-            "device": str(dev)}
+    res = {"config": 8, "metric": "events/sec (process-window median per key, ListState)",
+           "value": batch * steps / dt, "unit": "events/s", "ms_per_step": dt / steps * 1e3,
+           "p50_fire_step_ms": statistics.median(lat) if lat else None, "medians": rows,
+           "keys": keys, "events_per_step": batch, "window_values": batch * 12,
+           "device": str(dev)}
+    if quantiles:
+        res["metric"] = f"events/sec (process-window {len(ppm)} quantiles per key, ListState)"
+        res["quantiles_ppm"] = list(ppm)
+    return res
 
 
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
@@ -939,6 +951,9 @@ def main(argv=None) -> int:
     ap.add_argument("--latency-fire", type=int, default=0,
                     help="config 4: fire right away when at most this many windows are due "
                          "(latency-bounded mode; 0 = pipelined firing)")
+    ap.add_argument("--quantiles", default=None,
+                    help="config 8: comma-separated quantiles in [0, 1] (e.g. 0.5,0.95,0.99) "
+                         "instead of the median")
     ap.add_argument("--threads", type=int, default=4,
                     help="config 1 CPU path: parse threads (the reference job runs at P = 4)")
     a = ap.parse_args(argv)
@@ -965,7 +980,8 @@ def main(argv=None) -> int:
         r = config9(lines=a.lines or 16_000_000, device=a.device,
                     batch_lines=a.batch or (1 << 20))
     elif a.config == 8:
-        r = config8(a.steps, a.warmup, a.batch or (1 << 22), device=a.device)
+        r = config8(a.steps, a.warmup, a.batch or (1 << 22), device=a.device,
+                    quantiles=[float(x) for x in a.quantiles.split(",")] if a.quantiles else None)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

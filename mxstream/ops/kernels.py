@@ -519,3 +519,39 @@ def segment_median(heads: torch.Tensor, ord_bits: torch.Tensor, *, sorted_values
     else:
         getattr(m, "cpu_" + name)(*args)
     return out
+
+
+MAX_QUANTILES = 8
+PPM_ONE = 1_000_000
+
+
+def check_ppm(ppm) -> tuple:
+    """1..8 quantiles in parts per million, each an integer in 0..1_000_000."""
+    ppm = tuple(ppm)
+    if not 1 <= len(ppm) <= MAX_QUANTILES:
+        raise ValueError(f"1 to {MAX_QUANTILES} quantiles per window, got {len(ppm)}")
+    for p in ppm:
+        if isinstance(p, bool) or not hasattr(p, "__index__") or not 0 <= int(p) <= PPM_ONE:
+            raise ValueError(f"quantile in parts per million must be an integer in 0..{PPM_ONE}: {p!r}")
+    return tuple(int(p) for p in ppm)
+
+
+def segment_quantiles(heads: torch.Tensor, ord_bits: torch.Tensor, ppm) -> torch.Tensor:
+    """Nearest-rank quantiles of every segment of unsorted order bits starting at `heads`:
+    float64 [Q, nseg], row j = the element at sorted index clamp(ceil(n * ppm[j] / 1e6) - 1, 0,
+    n - 1) of each segment (the element itself; 0.0 for an empty segment)."""
+    ppm = check_ppm(ppm)
+    dev = ord_bits.device
+    _check(heads, torch.int64, heads.numel(), "heads", dev)
+    _check(ord_bits, torch.int64, ord_bits.numel(), "ord", dev)
+    if heads.numel() and (int(heads[0]) != 0 or int(heads[-1]) >= max(1, ord_bits.numel())):
+        raise ValueError("segment heads out of range")
+    out = torch.empty((len(ppm), heads.numel()), dtype=torch.float64, device=dev)
+    m = load()
+    args = (heads.data_ptr(), heads.numel(), ord_bits.numel(), ord_bits.data_ptr(), list(ppm),
+            out.data_ptr())
+    if _is_gpu(ord_bits):
+        m.gpu_segment_quantile_select(*args, _stream(ord_bits))
+    else:
+        m.cpu_segment_quantile_select(*args)
+    return out

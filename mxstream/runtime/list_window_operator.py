@@ -13,7 +13,9 @@ a power-of-two ring of pane slots, each an append buffer of (key, f64 bits) on t
   totals and per-pane prefixes from the panes' counts (``lw_rank_prefix``), the order-preserving
   scan of the totals (``lw_scan``: offsets + the non-empty keys in key order), every element
   placed at segment start + prefix + rank (``lw_rank_scatter``, as order bits), and each
-  segment's median selected in LDS (``segment_median_select``). Panes without ranks (wide key
+  segment's median selected in LDS (``segment_median_select``) -- or, for
+  ``func=("quantiles", ppm)``, up to 8 nearest-rank quantiles from one staged copy of the
+  segment (``segment_quantile_select``). Panes without ranks (wide key
   ranges, restored panes) fire through a counting sort with atomics (``lw_key_count`` /
   ``lw_key_scatter``); key ranges over 16 Mi ids are mapped to dense ids first. No comparison
   sort of the window, no per-pane host loop.
@@ -44,10 +46,16 @@ def _next_pow2(x: int) -> int:
 
 class KeyedListWindowOperator:
     def __init__(self, *, size: int, slide: int | None = None, offset: int = 0,
-                 lateness: int = 0, device="cpu", time_mode: str = "event", func: str = "median"):
+                 lateness: int = 0, device="cpu", time_mode: str = "event", func="median"):
         slide = size if slide is None else slide
-        if func != "median":
-            raise ValueError("supported list-window functions: median")
+        # func: "median" (fired res = one f64 per key) or ("quantiles", (ppm, ...)) -- 1..8
+        # nearest-rank quantiles in parts per million (fired res = [Q, k] f64, row j = ppm[j]).
+        if func == "median":
+            self.ppm = None
+        elif isinstance(func, (tuple, list)) and len(func) == 2 and func[0] == "quantiles":
+            self.ppm = list(K.check_ppm(func[1]))
+        else:
+            raise ValueError('supported list-window functions: "median", ("quantiles", (ppm, ...))')
         self.size, self.slide, self.offset, self.lateness = int(size), int(slide), int(offset), int(lateness)
         self.pane = math.gcd(self.size, self.slide)
         self.ppw = self.size // self.pane
@@ -184,7 +192,8 @@ class KeyedListWindowOperator:
     # ---- ingest ---------------------------------------------------------------------------
     def process(self, keys: torch.Tensor, ts: torch.Tensor, vals_f64: torch.Tensor) -> list:
         """keys int64 (or int32 dictionary ids), ts int64, vals: f64 bit patterns (int64).
-        Returns fired rows (window_start, window_end, keys, medians) of late re-firings."""
+        Returns fired rows (window_start, window_end, keys, res) of late re-firings; res is
+        the medians [k], or the quantiles [Q, k]."""
         n = keys.numel()
         if n == 0:
             return []
@@ -314,23 +323,43 @@ class KeyedListWindowOperator:
             rhi = max(self.kbase[r] + self.kcnt[r].numel() for r in slots)
             ranked = rhi - rlo <= _MAX_DENSE
         if ranked:
-            keys_out, med = self._median_ranked(slots, rlo, rhi - rlo, total)
+            keys_out, med = self._fire_ranked(slots, rlo, rhi - rlo, total)
         elif kmin >= 0 and kmax - kmin < _MAX_DENSE and len(slots) <= 64:
-            keys_out, med = self._median_dense(slots, kmin, kmax - kmin + 1, total)
+            keys_out, med = self._fire_dense(slots, kmin, kmax - kmin + 1, total)
         else:
-            keys_out, med = self._median_mapped(slots)
+            keys_out, med = self._fire_mapped(slots)
         if only_keys is not None:
             sel = torch.isin(keys_out, only_keys.to(keys_out.device))
-            keys_out, med = keys_out[sel], med[sel]
+            keys_out, med = keys_out[sel], med[..., sel]  # the key axis is the last one
         if not keys_out.numel():
             return []
         self.metrics.num_records_out += int(keys_out.numel())
         return [(s, s + self.size, keys_out.cpu().numpy(), med.cpu().numpy())]
 
-    def _median_ranked(self, slots, kmin: int, nk: int, total: int):
+    def _select(self, heads: torch.Tensor, k: int, total: int, ordv: torch.Tensor) -> torch.Tensor:
+        """The window function over the k key segments of order bits in `ordv`: the medians
+        [k], or the nearest-rank quantiles [Q, k] (one column per quantile, one kernel)."""
+        m = self._m
+        shape = (k,) if self.ppm is None else (len(self.ppm), k)
+        res = torch.empty(shape, dtype=torch.float64, device=self.device)
+        if not k:
+            return res
+        args = (heads.data_ptr(), k, total, ordv.data_ptr())
+        if self.ppm is None:
+            if self.cuda:
+                m.gpu_segment_median_select(*args, res.data_ptr(), self._stream())
+            else:
+                m.cpu_segment_median_select(*args, res.data_ptr())
+        elif self.cuda:
+            m.gpu_segment_quantile_select(*args, self.ppm, res.data_ptr(), self._stream())
+        else:
+            m.cpu_segment_quantile_select(*args, self.ppm, res.data_ptr())
+        return res
+
+    def _fire_ranked(self, slots, kmin: int, nk: int, total: int):
         """Ranked firing: per-key totals and per-pane prefixes from the panes' counts, the
         order-preserving scan, then every element placed at segment start + prefix + rank (no
-        atomics), then the per-segment median."""
+        atomics), then the per-segment selection."""
         m, st, dev = self._m, self._stream(), self.device
         panes = [(self.kbuf[r].data_ptr(), self.vbuf[r].data_ptr(), self.rbuf[r].data_ptr(),
                   self.kcnt[r].data_ptr(), self.kbase[r], self.kcnt[r].numel(), self.fill[r])
@@ -349,16 +378,9 @@ class KeyedListWindowOperator:
         m.lw_rank_scatter(self.cuda, panes, kmin, nk, offs.data_ptr(), pre.data_ptr(),
                           ordv.data_ptr(), st)
         k = int(nh.item())
-        med = torch.empty(k, dtype=torch.float64, device=dev)
-        if k:
-            args = (heads.data_ptr(), k, total, ordv.data_ptr(), med.data_ptr())
-            if self.cuda:
-                m.gpu_segment_median_select(*args, st)
-            else:
-                m.cpu_segment_median_select(*args)
-        return hkeys[:k], med
+        return hkeys[:k], self._select(heads, k, total, ordv)
 
-    def _median_dense(self, slots, kmin: int, nk: int, total: int):
+    def _fire_dense(self, slots, kmin: int, nk: int, total: int):
         m, st, dev = self._m, self._stream(), self.device
         panes = [(self.kbuf[r].data_ptr(), self.vbuf[r].data_ptr(), self.fill[r]) for r in slots]
         counts = torch.zeros(nk, dtype=torch.int32, device=dev)
@@ -374,16 +396,9 @@ class KeyedListWindowOperator:
         ordv = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
         m.lw_key_scatter(self.cuda, panes, kmin, cursor.data_ptr(), ordv.data_ptr(), st)
         k = int(nh.item())
-        med = torch.empty(k, dtype=torch.float64, device=dev)
-        if k:
-            args = (heads.data_ptr(), k, total, ordv.data_ptr(), med.data_ptr())
-            if self.cuda:
-                m.gpu_segment_median_select(*args, st)
-            else:
-                m.cpu_segment_median_select(*args)
-        return hkeys[:k], med
+        return hkeys[:k], self._select(heads, k, total, ordv)
 
-    def _median_mapped(self, slots):
+    def _fire_mapped(self, slots):
         """Keys outside a dense id range: dense ids by torch.unique, then the same firing."""
         keys = torch.cat([self.kbuf[r][:self.fill[r]] for r in slots])
         vals = torch.cat([self.vbuf[r][:self.fill[r]] for r in slots])
@@ -405,13 +420,7 @@ class KeyedListWindowOperator:
         cursor = offs[:nk].clone()
         ordv = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         m.lw_key_scatter(self.cuda, panes, 0, cursor.data_ptr(), ordv.data_ptr(), st)
-        med = torch.empty(nk, dtype=torch.float64, device=dev)
-        args = (heads.data_ptr(), nk, n, ordv.data_ptr(), med.data_ptr())
-        if self.cuda:
-            m.gpu_segment_median_select(*args, st)
-        else:
-            m.cpu_segment_median_select(*args)
-        return uniq, med
+        return uniq, self._select(heads, nk, n, ordv)
 
     # ---- checkpoints ------------------------------------------------------------------------
     def snapshot_state(self):

@@ -1267,9 +1267,12 @@ class NativeMedianOp(NativeWindowOp):
     """``process(<median>)`` windows (ComputeCpuMiddle.java:34-48) on the device list-window
     operator (runtime/list_window_operator.py): elements stay in a device pane arena, a firing
     counting-sorts the window by key id and a kernel selects each key's median.
+    ``process(WindowQuantiles(field, qs))`` (kind "quantiles") runs on the same arena: the
+    kernel selects the Q nearest-rank quantiles of each key and the rows are (key, x_1..x_Q).
     Checkpoints carry the live panes' elements (NativeWindowOp.snapshot -> snapshot_state)."""
 
     _key32_ok = False
+    quantiles_ppm = None  # planner: the quantiles (parts per million) of kind "quantiles"
 
     def _build(self, sample_val, dense: bool = False) -> bool:
         from .list_window_operator import KeyedListWindowOperator
@@ -1281,7 +1284,8 @@ class NativeMedianOp(NativeWindowOp):
         self.op = KeyedListWindowOperator(
             size=a.size, slide=a.slide, offset=a.offset,
             lateness=self.lateness if a.is_event_time() else 0, device=torch.device(self.device),
-            time_mode="event" if a.is_event_time() else "processing")
+            time_mode="event" if a.is_event_time() else "processing",
+            func=("quantiles", self.quantiles_ppm) if self.kind == "quantiles" else "median")
         comm = getattr(self, "comm", None)
         if comm is not None and comm.world > 1:
             # G > 1: the pane arena holds this rank's key groups; records reach their owner by
@@ -1320,6 +1324,8 @@ class NativeMedianOp(NativeWindowOp):
         fired = [f for f in fired if len(f[2])]
         if not fired:
             return []
+        if self.kind == "quantiles":
+            return self._emit_quantiles(fired)
         if self.scalar_result:
             keys = np.concatenate([np.asarray(f[2]) for f in fired]).astype(np.int64)
             med = np.concatenate([np.asarray(f[3]) for f in fired]).astype(np.float64)
@@ -1338,6 +1344,18 @@ class NativeMedianOp(NativeWindowOp):
                 sub = (flink_murmur(java_hash(key_obj)) % MP) * P // MP
                 out.append(Rec(value, e - 1, sub))
         return out
+
+    def _emit_quantiles(self, fired) -> list:
+        """(key, x_1..x_Q) rows of all fired windows as one ColumnBatch of (key kind,
+        FK_DOUBLE x Q): the print sink formats it in bulk, any other operator gets its Recs."""
+        keys = np.concatenate([np.asarray(f[2]) for f in fired]).astype(np.int64)
+        qs = np.concatenate([np.asarray(f[3], dtype=np.float64) for f in fired], axis=1)
+        ts = np.repeat(np.array([f[1] - 1 for f in fired], dtype=np.int64),
+                       [len(f[2]) for f in fired])
+        cols = [keys] + [np.ascontiguousarray(row) for row in qs]
+        kinds = (FK_STR if self.str_keys else FK_LONG,) + (FK_DOUBLE,) * qs.shape[0]
+        return [ColumnBatch(int(keys.size), cols, kinds, self.dict if self.str_keys else None, ts,
+                            self._subtasks(keys), False)]
 
 
 class NativeVectorWindowOp(NativeWindowOp):
