@@ -1008,6 +1008,40 @@ PYBIND11_MODULE(_mxs_native, m) {
     cpu::segment_quantile_select(P<int64_t>(heads), nseg, total, P<uint64_t>(ord), qs,
                                  P<double>(out));
   });
+  // Top-N cut of fired windows. cols / out: (keys, vals, raw, cnt) addresses, raw / cnt may be 0;
+  // plan: (src, smallest, key32, nwin, n, cap).
+  using TopnAddrs = std::tuple<intptr_t, intptr_t, intptr_t, intptr_t>;
+  using TopnArgs = std::tuple<int, bool, bool, int, int64_t, int64_t>;
+  auto topn_cols = [](const TopnAddrs& a) {
+    return TopnCols{P<void>(std::get<0>(a)), P<double>(std::get<1>(a)), P<uint64_t>(std::get<2>(a)),
+                    P<uint32_t>(std::get<3>(a))};
+  };
+  auto topn_plan = [](const TopnArgs& a) {
+    TopnPlan p{};
+    p.src = std::get<0>(a);
+    p.smallest = std::get<1>(a) ? 1 : 0;
+    p.key32 = std::get<2>(a) ? 1 : 0;
+    p.nwin = std::get<3>(a);
+    p.n = std::get<4>(a);
+    p.cap = std::get<5>(a);
+    return p;
+  };
+  m.attr("TOPN_BLOCK") = kTopnBlock;
+  m.attr("TOPN_MAX_WIN") = kTopnMaxWin;
+  m.def("topn_scratch_bytes", [](int nwin) { return (int64_t)topn_scratch_bytes(nwin); });
+  m.def("topn_source", [](int agg, bool has_map) { return (int)topn_source(agg, has_map); });
+  m.def("gpu_topn_select", [topn_cols, topn_plan](TopnAddrs in, intptr_t bounds, TopnArgs plan,
+                                                  TopnAddrs out, intptr_t out_bounds,
+                                                  intptr_t scratch, intptr_t stream) {
+    gpu::topn_select(topn_cols(in), P<uint32_t>(bounds), topn_plan(plan), topn_cols(out),
+                     P<uint32_t>(out_bounds), P<void>(scratch), stream);
+  });
+  m.def("cpu_topn_select", [topn_cols, topn_plan](TopnAddrs in, intptr_t bounds, TopnArgs plan,
+                                                  TopnAddrs out, intptr_t out_bounds) {
+    const TopnPlan p = topn_plan(plan);
+    py::gil_scoped_release nogil;
+    cpu::topn_select(topn_cols(in), P<uint32_t>(bounds), p, topn_cols(out), P<uint32_t>(out_bounds));
+  });
   m.def("gpu_segment_median", [](intptr_t heads, int64_t nseg, int64_t total, intptr_t ord,
                                  intptr_t out, intptr_t stream) {
     gpu::segment_median(P<int64_t>(heads), nseg, total, P<uint64_t>(ord), P<double>(out), stream);

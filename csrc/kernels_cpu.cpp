@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <thread>
 #include <vector>
@@ -587,6 +588,41 @@ void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
       std::nth_element(v.begin(), v.begin() + r, v.end());
       out[(int64_t)j * nseg + sg] = as_f64(f64_from_order_bits(v[r]));
     }
+  }
+}
+
+void topn_select(const TopnCols& in, const uint32_t* bounds, const TopnPlan& p,
+                 const TopnCols& out, uint32_t* out_bounds) {
+  if (const char* bad = topn_check(in, p, out)) throw std::invalid_argument(bad);
+  const uint64_t* vbits = reinterpret_cast<const uint64_t*>(in.vals);
+  auto word = [&](int64_t i) {
+    const uint64_t x = p.src == TOP_SRC_CNT ? (uint64_t)in.cnt[i] : p.src == TOP_SRC_I64 ? in.raw[i] : vbits[i];
+    return topn_order_word(p.src, x, p.smallest != 0);
+  };
+  std::vector<uint64_t> v;
+  int64_t q = 0;
+  for (int w = 0; w < p.nwin; ++w) {
+    const int64_t lo = std::min<int64_t>(w ? bounds[w - 1] : 0, p.cap);
+    const int64_t hi = std::max(lo, std::min<int64_t>(bounds[w], p.cap)), n = hi - lo;
+    uint64_t T = 0;
+    if (n > p.n) {
+      v.resize((size_t)n);
+      for (int64_t i = 0; i < n; ++i) v[(size_t)i] = word(lo + i);
+      std::nth_element(v.begin(), v.begin() + (p.n - 1), v.end(), std::greater<uint64_t>());
+      T = v[(size_t)(p.n - 1)];
+    }
+    for (int64_t s = lo; s < hi; ++s) {
+      if (word(s) < T) continue;
+      if (p.key32)
+        reinterpret_cast<uint32_t*>(out.keys)[q] = reinterpret_cast<const uint32_t*>(in.keys)[s];
+      else
+        reinterpret_cast<uint64_t*>(out.keys)[q] = reinterpret_cast<const uint64_t*>(in.keys)[s];
+      reinterpret_cast<uint64_t*>(out.vals)[q] = vbits[s];
+      if (out.raw) out.raw[q] = in.raw[s];
+      if (out.cnt) out.cnt[q] = in.cnt[s];
+      ++q;
+    }
+    out_bounds[w] = (uint32_t)q;
   }
 }
 

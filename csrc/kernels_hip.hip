@@ -4309,6 +4309,196 @@ __global__ __launch_bounds__(256) void segment_quantile_select_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Top-N cut of fired windows (mxs_common.h topn_order_word; mxs_kernels.h TopnPlan). Per window
+// an MSB-first radix select of the N-th largest order word T: 8 passes, each a 256-bin
+// histogram of the rows matching the prefix found so far (LDS per workgroup, one global atomic
+// per non-empty bin and workgroup) and a one-wave step that picks the digit; then every row
+// with a word >= T is compacted (ballot + scan, one reservation per workgroup and tile). The
+// windows of a batch are blockIdx.y; a window's rows are read from the device bounds, so the
+// grids are sized from the capacity and nothing is read on the host. A window with n <= N rows
+// skips the select: all of its rows pass.
+// State words of window w (kTopnStateWords): hist[8][256], then prefix (u64), rank, count,
+// cursor.
+// ------------------------------------------------------------------------------------------
+constexpr int kTopnMeta = 8 * 256;
+
+__device__ __forceinline__ void topn_range(const uint32_t* __restrict__ bounds, int w, int64_t cap,
+                                           uint32_t* lo, uint32_t* hi) {
+  const uint32_t c = (uint32_t)(cap < 0xFFFFFFFFll ? cap : 0xFFFFFFFFll);
+  const uint32_t a = w ? bounds[w - 1] : 0u, b = bounds[w];
+  *lo = a < c ? a : c;
+  *hi = b < c ? b : c;
+  if (*hi < *lo) *hi = *lo;
+}
+
+__device__ __forceinline__ uint64_t topn_word(const TopnCols& c, const TopnPlan& p, int64_t i) {
+  const uint64_t x = p.src == TOP_SRC_CNT   ? (uint64_t)c.cnt[i]
+                     : p.src == TOP_SRC_I64 ? c.raw[i]
+                                            : reinterpret_cast<const uint64_t*>(c.vals)[i];
+  return topn_order_word(p.src, x, p.smallest != 0);
+}
+
+__global__ __launch_bounds__(256) void topn_init_kernel(uint32_t* __restrict__ state, int nwin,
+                                                        uint32_t rank0) {
+  const int64_t total = (int64_t)nwin * kTopnStateWords;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
+    state[i] = (i % kTopnStateWords) == kTopnMeta + 2 ? rank0 : 0u;
+}
+
+__global__ __launch_bounds__(kTopnBlock) void topn_hist_kernel(TopnCols in,
+                                                               const uint32_t* __restrict__ bounds,
+                                                               TopnPlan p, uint32_t* __restrict__ state,
+                                                               int pass) {
+  const int w = blockIdx.y;
+  uint32_t lo, hi;
+  topn_range(bounds, w, p.cap, &lo, &hi);
+  const int64_t n = (int64_t)hi - lo;
+  if (n <= p.n) return;
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t* st = state + (size_t)w * kTopnStateWords;
+  const uint64_t prefix = *reinterpret_cast<const uint64_t*>(st + kTopnMeta);
+  const int shift = 56 - 8 * pass;
+  const uint64_t mask = pass ? ~0ull << (shift + 8) : 0ull;
+  const int lane = threadIdx.x & 63;
+  for (int64_t base = (int64_t)blockIdx.x * kTopnBlock; base < n; base += (int64_t)gridDim.x * kTopnBlock) {
+    const int64_t i = base + threadIdx.x;
+    bool m = false;
+    uint32_t d = 0;
+    if (i < n) {
+      const uint64_t o = topn_word(in, p, lo + i);
+      m = (o & mask) == prefix;
+      d = (uint32_t)(o >> shift) & 255u;
+    }
+    // Most rows of a pass share one digit while the prefix is still long (small sums: the high
+    // bytes are equal): the lanes that agree with the first matching lane add once.
+    const unsigned long long any = __ballot(m);
+    if (any) {
+      const int leader = __ffsll((long long)any) - 1;
+      const uint32_t d0 = __shfl(d, leader);
+      const unsigned long long same = __ballot(m && d == d0);
+      if (m) {
+        if (d != d0) atomicAdd(&h[d], 1u);
+        else if (lane == leader) atomicAdd(&h[d0], (uint32_t)__popcll(same));
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t c = h[threadIdx.x];
+  if (c) atomicAdd(&st[pass * 256 + threadIdx.x], c);
+}
+
+// One wave per window: the digit of this pass = the bin (from 255 down) that holds the row of
+// remaining rank r; prefix and r move on. The last pass leaves T in the prefix and the exact
+// candidate count (rows above T = N - 1 - r, rows equal to T = the chosen bin).
+__global__ __launch_bounds__(64) void topn_pick_kernel(const uint32_t* __restrict__ bounds,
+                                                       TopnPlan p, uint32_t* __restrict__ state,
+                                                       int pass) {
+  const int w = blockIdx.x, lane = threadIdx.x;
+  uint32_t lo, hi;
+  topn_range(bounds, w, p.cap, &lo, &hi);
+  const int64_t n = (int64_t)hi - lo;
+  uint32_t* st = state + (size_t)w * kTopnStateWords;
+  if (n <= p.n) {
+    if (pass == 7 && lane == 0) st[kTopnMeta + 3] = (uint32_t)n;
+    return;
+  }
+  const uint32_t* h = st + pass * 256;
+  const uint32_t r = st[kTopnMeta + 2];
+  uint32_t c[4], tot = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    c[j] = h[255 - (lane * 4 + j)];
+    tot += c[j];
+  }
+  uint32_t incl = tot;
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(incl, o);
+    if (lane >= o) incl += y;
+  }
+  const uint32_t excl = incl - tot;
+  if (r >= excl && r < incl) {  // exactly one lane: the histogram holds > N > r matching rows
+    uint32_t rr = r - excl;
+    int bin = 0;
+    uint32_t cb = 0;
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (!found) {
+        if (rr < c[j]) {
+          bin = 255 - (lane * 4 + j);
+          cb = c[j];
+          found = true;
+        } else {
+          rr -= c[j];
+        }
+      }
+    }
+    uint64_t* pre = reinterpret_cast<uint64_t*>(st + kTopnMeta);
+    *pre |= (uint64_t)bin << (56 - 8 * pass);
+    st[kTopnMeta + 2] = rr;
+    if (pass == 7) st[kTopnMeta + 3] = (uint32_t)(p.n - 1 - rr) + cb;
+  }
+}
+
+__global__ __launch_bounds__(kTopnBlock) void topn_compact_kernel(TopnCols in,
+                                                                  const uint32_t* __restrict__ bounds,
+                                                                  TopnPlan p, uint32_t* __restrict__ state,
+                                                                  TopnCols out,
+                                                                  uint32_t* __restrict__ out_bounds) {
+  const int w = blockIdx.y;
+  __shared__ uint32_t s_off, wcnt[kTopnBlock / 64 + 1];
+  if (threadIdx.x < 64) {  // wave 0: candidates of the earlier windows
+    uint32_t c = 0;
+    for (int j = threadIdx.x; j < w; j += 64) c += state[(size_t)j * kTopnStateWords + kTopnMeta + 3];
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    if (threadIdx.x == 0) s_off = c;
+  }
+  __syncthreads();
+  uint32_t lo, hi;
+  topn_range(bounds, w, p.cap, &lo, &hi);
+  const int64_t n = (int64_t)hi - lo;
+  uint32_t* st = state + (size_t)w * kTopnStateWords;
+  const uint64_t T = n <= p.n ? 0ull : *reinterpret_cast<const uint64_t*>(st + kTopnMeta);
+  const uint32_t off = s_off;
+  if (blockIdx.x == 0 && threadIdx.x == 0) out_bounds[w] = off + st[kTopnMeta + 3];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  constexpr int nw = kTopnBlock / 64;
+  for (int64_t base = (int64_t)blockIdx.x * kTopnBlock; base < n; base += (int64_t)gridDim.x * kTopnBlock) {
+    const int64_t i = base + threadIdx.x;
+    const bool keep = i < n && topn_word(in, p, lo + i) >= T;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wcnt[wid] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t tot = 0;
+      for (int j = 0; j < nw; ++j) {
+        const uint32_t c = wcnt[j];
+        wcnt[j] = tot;
+        tot += c;
+      }
+      wcnt[nw] = tot ? atomicAdd(&st[kTopnMeta + 4], tot) : 0u;
+    }
+    __syncthreads();
+    if (keep) {
+      const int64_t q = (int64_t)off + wcnt[nw] + wcnt[wid] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (q < p.cap) {
+        const int64_t s = lo + i;
+        if (p.key32)
+          reinterpret_cast<uint32_t*>(out.keys)[q] = reinterpret_cast<const uint32_t*>(in.keys)[s];
+        else
+          reinterpret_cast<uint64_t*>(out.keys)[q] = reinterpret_cast<const uint64_t*>(in.keys)[s];
+        out.vals[q] = in.vals[s];
+        if (out.raw) out.raw[q] = in.raw[s];
+        if (out.cnt) out.cnt[q] = in.cnt[s];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 int grid_for(int64_t n, int block, int max_blocks) {
   int64_t g = (n + block - 1) / block;
   if (g < 1) g = 1;
@@ -5745,6 +5935,29 @@ void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
   if (nseg <= 0) return;
   hipLaunchKernelGGL(segment_quantile_select_kernel, dim3(grid_for(nseg, 4, 16384)), dim3(256), 0,
                      (hipStream_t)stream, heads, nseg, total, ord, qs, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void topn_select(const TopnCols& in, const uint32_t* bounds, const TopnPlan& p,
+                 const TopnCols& out, uint32_t* out_bounds, void* scratch, intptr_t stream) {
+  if (const char* bad = topn_check(in, p, out)) throw std::invalid_argument(bad);
+  if (p.nwin <= 0) return;
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t* state = reinterpret_cast<uint32_t*>(scratch);
+  const uint32_t rank0 = (uint32_t)std::min<int64_t>(p.n - 1, 0xFFFFFFFFll);
+  hipLaunchKernelGGL(topn_init_kernel, dim3(grid_for((int64_t)p.nwin * kTopnStateWords, 256, 1024)),
+                     dim3(256), 0, s, state, p.nwin, rank0);
+  HIP_CHECK(hipGetLastError());
+  // ~1024 workgroups over the batch (4 per CU), each window's rows in grid-stride tiles.
+  const dim3 grid(grid_for(p.cap, kTopnBlock * 4, std::max(1, 1024 / p.nwin)), p.nwin);
+  for (int pass = 0; pass < 8; ++pass) {
+    hipLaunchKernelGGL(topn_hist_kernel, grid, dim3(kTopnBlock), 0, s, in, bounds, p, state, pass);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(topn_pick_kernel, dim3(p.nwin), dim3(64), 0, s, bounds, p, state, pass);
+    HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(topn_compact_kernel, grid, dim3(kTopnBlock), 0, s, in, bounds, p, state, out,
+                     out_bounds);
   HIP_CHECK(hipGetLastError());
 }
 

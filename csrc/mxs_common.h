@@ -799,4 +799,23 @@ MXS_HD int64_t quantile_rank(int64_t n, uint32_t ppm) {
   return idx < 0 ? 0 : (idx > n - 1 ? n - 1 : idx);
 }
 
+// Top-N windows (topn_select): every fired row is ranked by one 64-bit order word, larger =
+// better. The word's source is fixed per operator: the raw accumulator of an integer sum / min /
+// max without a map program (signed order), the count of a count aggregate, else the mapped f64
+// value (Double.compare order: -0.0 < 0.0, NaN last). `smallest` reverses the order. Rows with a
+// word >= the N-th largest word of their window are the window's candidates; ties at that
+// threshold all pass (the host settles them by key), so no layer ever breaks a tie by position.
+enum TopSrc : int32_t { TOP_SRC_F64 = 0, TOP_SRC_I64 = 1, TOP_SRC_CNT = 2 };
+MXS_HD int32_t topn_source(int32_t agg, bool has_map) {
+  if (has_map) return TOP_SRC_F64;
+  if (agg == AGG_COUNT) return TOP_SRC_CNT;
+  return (agg == AGG_SUM_I64 || agg == AGG_MIN_I64 || agg == AGG_MAX_I64) ? TOP_SRC_I64 : TOP_SRC_F64;
+}
+// x: the source's bits (f64 bit pattern, int64 accumulator, or the count zero-extended).
+MXS_HD uint64_t topn_order_word(int32_t src, uint64_t x, bool smallest) {
+  const uint64_t o = src == TOP_SRC_F64 ? f64_order_bits(x)
+                     : src == TOP_SRC_I64 ? (x ^ 0x8000000000000000ull) : x;
+  return smallest ? ~o : o;
+}
+
 }  // namespace mxs

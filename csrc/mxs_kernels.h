@@ -150,6 +150,42 @@ struct D2HBatch {
   const uint32_t* n_dev;  // device row count (fired rows), read by the copy kernel; may be null
 };
 
+// Top-N cut of fired windows (topn_select; order word and candidate rule: mxs_common.h). The
+// fired columns hold nwin windows back to back, bounds[w] = rows of windows 0..w (device memory,
+// as window_fire_many writes them; one window: its row count). Rows past `cap` do not exist.
+struct TopnPlan {
+  int32_t src;       // TopSrc: vals (f64), raw (int64) or cnt
+  int32_t smallest;  // 1: the N smallest
+  int32_t key32;     // keys are uint32 (FirePlan.key32)
+  int32_t nwin;
+  int64_t n;         // N >= 1
+  int64_t cap;       // rows readable in the input columns and writable in the output columns
+};
+struct TopnCols {    // raw / cnt may be null (the order source's column may not)
+  void* keys;
+  double* vals;
+  uint64_t* raw;
+  uint32_t* cnt;
+};
+constexpr int kTopnBlock = 256;
+constexpr int kTopnMaxWin = 1024;
+// Device scratch words per window: 8 passes x 256 histogram bins + {threshold prefix (2 words),
+// remaining rank, candidate count, output cursor, 3 spare}.
+constexpr int kTopnStateWords = 8 * 256 + 8;
+inline size_t topn_scratch_bytes(int nwin) { return (size_t)nwin * kTopnStateWords * 4; }
+// Argument check shared by the kernel launcher and the C++ twin; the message or null.
+inline const char* topn_check(const TopnCols& in, const TopnPlan& p, const TopnCols& out) {
+  if (p.n < 1) return "topn_select: n must be >= 1";
+  if (p.nwin < 0 || p.nwin > kTopnMaxWin) return "topn_select: 0..1024 windows";
+  if (p.cap < 0 || p.cap >= ((int64_t)1 << 32)) return "topn_select: capacity must be below 2^32 rows";
+  if (p.src < TOP_SRC_F64 || p.src > TOP_SRC_CNT) return "topn_select: unknown order source";
+  if (!in.keys || !in.vals || !out.keys || !out.vals) return "topn_select: null key / value column";
+  if (p.src == TOP_SRC_I64 && !in.raw) return "topn_select: the raw column is the order source";
+  if (p.src == TOP_SRC_CNT && !in.cnt) return "topn_select: the count column is the order source";
+  if ((out.raw && !in.raw) || (out.cnt && !in.cnt)) return "topn_select: output column without input";
+  return nullptr;
+}
+
 constexpr int64_t kRollHistMaxSlots = 16384;  // LDS running-count table of the emit pass
 
 // Order-preserving compaction tiles (filter_mask / line_starts / ingest masks): a 256-thread
@@ -374,6 +410,12 @@ void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total,
 void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
                              const uint64_t* ord, const QuantileSpec& qs, double* out,
                              intptr_t stream);
+// Candidates of every window (order word >= the window's N-th largest) -> `out`, contiguous in
+// window order, any order inside a window; out_bounds[w] = candidates of windows 0..w. Radix
+// select over the order words (8 byte passes), row counts read on the device, no host sync.
+// scratch: topn_scratch_bytes(p.nwin), contents irrelevant.
+void topn_select(const TopnCols& in, const uint32_t* bounds, const TopnPlan& p,
+                 const TopnCols& out, uint32_t* out_bounds, void* scratch, intptr_t stream);
 void set_erase(uint64_t* set, uint32_t mask, const int64_t* keys, int64_t n, intptr_t stream);
 void set_insert_keys(uint64_t* set, uint32_t mask, const int64_t* keys, int64_t n,
                      intptr_t stream);
@@ -532,6 +574,8 @@ void table_insert(const uint64_t* keys, int64_t n, int nsub_log2, int cap_log2, 
 void window_combine(const Rec* recs, const uint32_t* counts, int nbuckets, const AggPlan& plan,
                     Rec* out, uint32_t ccap, uint32_t* out_counts, uint32_t* flags);
 void f64_order_bits(const uint64_t* v, int64_t n, uint64_t* o);
+void topn_select(const TopnCols& in, const uint32_t* bounds, const TopnPlan& p,
+                 const TopnCols& out, uint32_t* out_bounds);
 void segment_median(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
                     double* out);
 void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total,

@@ -4,6 +4,7 @@
 // (partition -> window_agg -> fire), the vector-metric windows and the table checker, on
 // adversarial shapes: tiny sub-tables, late data, bucket counts at capacity, empty batches.
 // Exit code 0 and no sanitizer report = pass (tests/test_debug.py).
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -117,6 +118,31 @@ int main() {
     cpu::window_fire(keys_g.data(), acc_g.data(), cnt_g.data(), dirty_g.data(), fp,
                      out_keys.data(), out_vals.data(), out_raw.data(), out_cnt.data(),
                      out_n.data());
+    {
+      // Top-N cut of the fired rows (topn_select twin): two windows, the second bound past the
+      // capacity (clamped); by raw sum with every column, then by value with the compact
+      // layout's null raw / cnt columns and the N smallest.
+      std::vector<uint64_t> tk(nslots), tr(nslots);
+      std::vector<double> tv(nslots);
+      std::vector<uint32_t> tc(nslots), tb(2);
+      const uint32_t b2[2] = {out_n[0] / 2, (uint32_t)nslots + 7};
+      TopnPlan tp;
+      std::memset(&tp, 0, sizeof(tp));
+      tp.src = TOP_SRC_I64;
+      tp.nwin = 2;
+      tp.n = 10;
+      tp.cap = (int64_t)nslots;
+      const TopnCols in{out_keys.data(), out_vals.data(), out_raw.data(), out_cnt.data()};
+      cpu::topn_select(in, b2, tp, TopnCols{tk.data(), tv.data(), tr.data(), tc.data()}, tb.data());
+      if (tb[0] < std::min<uint32_t>(10, b2[0]) || tb[1] - tb[0] < 10 || tb[1] > nslots)
+        return fail("topn_select: candidate bounds");
+      tp.src = TOP_SRC_F64;
+      tp.smallest = 1;
+      tp.n = 1;
+      cpu::topn_select(TopnCols{out_keys.data(), out_vals.data(), nullptr, nullptr}, b2, tp,
+                       TopnCols{tk.data(), tv.data(), nullptr, nullptr}, tb.data());
+      if (b2[0] && tb[0] < 1) return fail("topn_select: empty cut");
+    }
     VecFirePlan vf;
     std::memset(&vf, 0, sizeof(vf));
     vf.dim = dim;

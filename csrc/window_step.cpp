@@ -180,6 +180,16 @@ WindowStep::WindowStep(const WindowStepConfig& c, std::shared_ptr<StepComm> comm
   rank_ = comm_ ? comm_->rank : 0;
   if (c.agg < AGG_SUM_I64 || c.agg > AGG_AVG_I64) throw std::invalid_argument("unknown aggregate");
   if (c.ooo_bound < 0) throw std::invalid_argument("negative out-of-orderness bound");
+  if (c.top_n < 0) throw std::invalid_argument("top_n must be >= 1 (0 = off)");
+  if (c.top_n > 0) {
+    // The cut covers the plain firing path only: re-firings, the partials exchange, the spill
+    // tier and vector rows would each need their own.
+    if (world_ > 1) throw std::invalid_argument("top_n needs a single rank (world > 1)");
+    if (c.spill) throw std::invalid_argument("top_n does not combine with spill");
+    if (c.dim > 0) throw std::invalid_argument("top_n does not combine with vector windows (dim > 0)");
+    if (c.lateness > 0) throw std::invalid_argument("top_n does not combine with lateness > 0");
+    if (c.side_output_late) throw std::invalid_argument("top_n does not combine with side_output_late");
+  }
   if (gpu_) hip_ok(hipSetDevice(c.device_index), "hipSetDevice");
   const bool vec = c.dim > 0;
   parallelism_ = c.parallelism > 0 ? c.parallelism : world_;
@@ -285,6 +295,18 @@ WindowStep::WindowStep(const WindowStepConfig& c, std::shared_ptr<StepComm> comm
   out_cnt_ = mem_alloc(orows_ * 4, dk, false);
   fire_bounds_ = mem_alloc(((std::max(fire_group_, 32) + 3) & ~3) * 4, dk);
   hbounds_ = mem_alloc(std::max(fire_group_, 32) * 4, gpu_ ? 2 : 0);
+  if (c.top_n > 0) {
+    const bool kv = c.emit_kv && dense_bits_;
+    top_src_ = topn_source(c.agg, c.map.ncode > 0);
+    top_keys_ = mem_alloc(orows_ * 8, dk, false);
+    top_vals_ = mem_alloc(orows_ * 8, dk, false);
+    if (!kv) {
+      top_raw_ = mem_alloc(orows_ * 8, dk, false);
+      top_cnt_ = mem_alloc(orows_ * 4, dk, false);
+    }
+    top_bounds_ = mem_alloc(((std::max(fire_group_, 32) + 3) & ~3) * 4, dk);
+    if (gpu_) top_scratch_ = mem_alloc(topn_scratch_bytes(fire_group_), 1, false);
+  }
   async_fire_ = gpu_ && env_on("MXS_ASYNC_FIRE", true);
   if (async_fire_ && env_on("MXS_COPY_STREAM", true))
     hip_ok(hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking), "stream");
@@ -1352,8 +1374,9 @@ std::vector<FireRows> WindowStep::take(bool block) {
       host_wait(fb.ev);
       const uint32_t* hf = (const uint32_t*)((char*)fb.slab->p + fb.flags_off);
       check_fire_flags(hf);
+      if (cfg_.top_n > 0) m_.topn_rows_in += std::min<int64_t>(hf[2], fb.ncap);
       if (fb.bounds) {
-        const uint32_t* hb = (const uint32_t*)((char*)fb.slab->p + fb.bounds_off);
+        const uint32_t* hb =(const uint32_t*)((char*)fb.slab->p + fb.bounds_off);
         fb.hb.assign(hb, hb + fb.wins.size());
       } else {
         fb.hb.assign(1, hf[2]);
@@ -1432,15 +1455,17 @@ void WindowStep::fire_window(int64_t s, bool only_dirty, int64_t seq) {
   }
   fp.key32 = kv ? 1 : 0;
   uint32_t* on = P<uint32_t>(flags_) + 2;
+  // (compact rows skip raw / cnt unless the top-N cut ranks by one of them)
+  uint64_t* fraw = kv && !(cfg_.top_n > 0 && top_src_ == TOP_SRC_I64) ? nullptr : P<uint64_t>(out_raw_);
+  uint32_t* fcnt = kv && !(cfg_.top_n > 0 && top_src_ == TOP_SRC_CNT) ? nullptr : P<uint32_t>(out_cnt_);
   if (gpu_)
     gpu::window_fire(P<uint64_t>(keys_g_), P<uint64_t>(acc_g_), P<uint32_t>(cnt_g_),
                      P<uint8_t>(dirty_g_), fp, P<uint64_t>(out_keys_), P<double>(out_vals_),
-                     kv ? nullptr : P<uint64_t>(out_raw_), kv ? nullptr : P<uint32_t>(out_cnt_), on,
-                     (intptr_t)cur_);
+                     fraw, fcnt, on, (intptr_t)cur_);
   else
     cpu::window_fire(P<uint64_t>(keys_g_), P<uint64_t>(acc_g_), P<uint32_t>(cnt_g_),
                      P<uint8_t>(dirty_g_), fp, P<uint64_t>(out_keys_), P<double>(out_vals_),
-                     kv ? nullptr : P<uint64_t>(out_raw_), kv ? nullptr : P<uint32_t>(out_cnt_), on);
+                     fraw, fcnt, on);
   ++m_.num_fires;
   FireBatch fb;
   fb.wins = {s};
@@ -1450,6 +1475,22 @@ void WindowStep::fire_window(int64_t s, bool only_dirty, int64_t seq) {
   std::vector<std::pair<const void*, int>> cols;
   if (kv) cols = {{out_keys_->p, 4}, {out_vals_->p, 8}};
   else cols = {{out_keys_->p, 8}, {out_vals_->p, 8}, {out_raw_->p, 8}, {out_cnt_->p, 4}};
+  if (cfg_.top_n > 0) {
+    // The window's candidates leave in place of its rows; their count is the one bound.
+    top_cut(on, 1, kv, &cols);
+    uint32_t* tb = P<uint32_t>(top_bounds_);
+    fb.bounds = true;
+    if (async_fire_) {
+      queue_counted(std::move(fb), cols, orows_, tb, true, tb, 1, &out_busy_);
+      return;
+    }
+    m_.topn_rows_in += std::min<int64_t>(fired_count(), orows_);
+    uint32_t nc = 0;
+    to_host_sync(&nc, tb, 4);
+    if (nc == 0) return;
+    queue_sync(std::move(fb), cols, nc, {nc});
+    return;
+  }
   if (async_fire_) {
     queue_counted(std::move(fb), cols, orows_, on, false, nullptr, 1, &out_busy_);
     return;
@@ -1457,6 +1498,26 @@ void WindowStep::fire_window(int64_t s, bool only_dirty, int64_t seq) {
   const uint32_t n = (uint32_t)std::min<int64_t>(fired_count(), orows_);
   if (n == 0) return;
   queue_sync(std::move(fb), cols, n, {n});
+}
+
+void WindowStep::top_cut(const uint32_t* bounds, int nwin, bool kv,
+                         std::vector<std::pair<const void*, int>>* cols) {
+  TopnPlan p;
+  std::memset(&p, 0, sizeof(p));
+  p.src = top_src_;
+  p.smallest = cfg_.top_smallest ? 1 : 0;
+  p.key32 = kv ? 1 : 0;
+  p.nwin = nwin;
+  p.n = cfg_.top_n;
+  p.cap = orows_;
+  const TopnCols in{out_keys_->p, P<double>(out_vals_), P<uint64_t>(out_raw_), P<uint32_t>(out_cnt_)};
+  const TopnCols out{top_keys_->p, P<double>(top_vals_), P<uint64_t>(top_raw_), P<uint32_t>(top_cnt_)};
+  if (gpu_)
+    gpu::topn_select(in, bounds, p, out, P<uint32_t>(top_bounds_), top_scratch_->p, (intptr_t)cur_);
+  else
+    cpu::topn_select(in, bounds, p, out, P<uint32_t>(top_bounds_));
+  if (kv) *cols = {{top_keys_->p, 4}, {top_vals_->p, 8}};
+  else *cols = {{top_keys_->p, 8}, {top_vals_->p, 8}, {top_raw_->p, 8}, {top_cnt_->p, 4}};
 }
 
 void WindowStep::fire_many(const std::vector<int64_t>& starts, bool only_dirty, int64_t seq) {
@@ -1508,6 +1569,11 @@ void WindowStep::fire_many(const std::vector<int64_t>& starts, bool only_dirty, 
   }
   if (gpu_) claim_flags();
   const int g = fire_group_;
+  const bool top = cfg_.top_n > 0;
+  const bool want_raw = !kv || (top && top_src_ == TOP_SRC_I64);
+  const bool want_cnt = !kv || (top && top_src_ == TOP_SRC_CNT);
+  uint64_t* fraw = want_raw ? P<uint64_t>(out_raw_) : nullptr;
+  uint32_t* fcnt = want_cnt ? P<uint32_t>(out_cnt_) : nullptr;
   for (size_t i = 0; i < wins.size(); i += g) {
     const int k = (int)std::min<size_t>(g, wins.size() - i);
     std::vector<int64_t> chunk(ws.begin() + i, ws.begin() + i + k);
@@ -1516,12 +1582,12 @@ void WindowStep::fire_many(const std::vector<int64_t>& starts, bool only_dirty, 
     if (gpu_) {
       claim_flags();  // the previous chunk's copy may still read out_* and the flags
       FireStage st{P<uint64_t>(stage_[0]), P<double>(stage_[1]),
-                   kv ? nullptr : P<uint64_t>(stage_[2]), kv ? nullptr : P<uint32_t>(stage_[3]),
+                   want_raw ? P<uint64_t>(stage_[2]) : nullptr,
+                   want_cnt ? P<uint32_t>(stage_[3]) : nullptr,
                    P<uint32_t>(stage_[4]), (uint32_t)nslots_};
       gpu::window_fire_many(P<uint64_t>(keys_g_), P<uint64_t>(acc_g_), P<uint32_t>(cnt_g_),
                             P<uint8_t>(dirty_g_), base, wins.data() + i, k, st, P<uint64_t>(out_keys_),
-                            P<double>(out_vals_), kv ? nullptr : P<uint64_t>(out_raw_),
-                            kv ? nullptr : P<uint32_t>(out_cnt_), on, bounds, (intptr_t)cur_);
+                            P<double>(out_vals_), fraw, fcnt, on, bounds, (intptr_t)cur_);
     } else {
       *on = 0;
       for (int j = 0; j < k; ++j) {
@@ -1532,7 +1598,7 @@ void WindowStep::fire_many(const std::vector<int64_t>& starts, bool only_dirty, 
         p.wend = wins[i + j].wend;
         cpu::window_fire(P<uint64_t>(keys_g_), P<uint64_t>(acc_g_), P<uint32_t>(cnt_g_),
                          P<uint8_t>(dirty_g_), p, P<uint64_t>(out_keys_), P<double>(out_vals_),
-                         kv ? nullptr : P<uint64_t>(out_raw_), kv ? nullptr : P<uint32_t>(out_cnt_), on);
+                         fraw, fcnt, on);
         bounds[j] = *on;
       }
     }
@@ -1546,6 +1612,10 @@ void WindowStep::fire_many(const std::vector<int64_t>& starts, bool only_dirty, 
     std::vector<std::pair<const void*, int>> cols;
     if (kv) cols = {{out_keys_->p, 4}, {out_vals_->p, 8}};
     else cols = {{out_keys_->p, 8}, {out_vals_->p, 8}, {out_raw_->p, 8}, {out_cnt_->p, 4}};
+    if (top) {  // the group's candidates and their bounds leave in place of its rows
+      top_cut(bounds, k, kv, &cols);
+      bounds = P<uint32_t>(top_bounds_);
+    }
     if (async_fire_) {
       queue_counted(std::move(fb), cols, orows_, bounds + (k - 1), true, bounds, k, &out_busy_);
       continue;
@@ -1555,6 +1625,7 @@ void WindowStep::fire_many(const std::vector<int64_t>& starts, bool only_dirty, 
     to_host_sync(hf, flags_->p, 16);
     to_host_sync(hb.data(), bounds, (size_t)k * 4);
     check_fire_flags(hf);
+    if (top) m_.topn_rows_in += std::min<int64_t>(hf[2], orows_);
     const int64_t n = std::min<int64_t>(hb.back(), orows_);
     if (n == 0) continue;
     queue_sync(std::move(fb), cols, n, std::move(hb));

@@ -95,6 +95,11 @@ struct WindowStepConfig {
   bool emit_kv = false;
   int latency_fire = 0;
   int64_t window_keys = -1;
+  // Top-N cut of every firing (0 = off): only the rows whose order word (mxs_common.h
+  // topn_order_word) is >= the window's N-th largest -- with top_smallest, <= its N-th smallest
+  // -- leave the device; ties at the threshold all leave, the consumer settles them.
+  int64_t top_n = 0;
+  bool top_smallest = false;
   // Vector windows (runtime/vector_window_operator.py): dim > 0 keeps one f32 vector per (key,
   // pane) and fires the per-key sum / average vector (csrc/vector_hip.hip, MFMA).
   int dim = 0;
@@ -151,6 +156,7 @@ struct StepMetrics {
   int64_t compact_fallbacks = 0, latency_fires = 0, combine_regrows = 0, a2a_bytes = 0;
   int64_t payload_bytes = 0, merge_compactions = 0, async_evictions = 0, dropped_keys = 0;
   int64_t spilled_keys = 0, spilled_rows = 0;
+  int64_t topn_rows_in = 0;  // rows the fire kernels produced ahead of the top-N cut
 };
 
 class WindowStep {
@@ -305,6 +311,10 @@ class WindowStep {
                             int64_t seq);
   void fire_window_tiered(int64_t s, int64_t p0, int64_t p1, bool only_dirty, int64_t seq);
   void fire_window_vector(int64_t s, int64_t p0, int64_t p1, bool only_dirty, int64_t seq);
+  // Top-N cut of the rows a plain firing just wrote to out_*: candidates -> top_*, bounds ->
+  // top_bounds_; `cols` is replaced by the candidate columns.
+  void top_cut(const uint32_t* bounds, int nwin, bool kv,
+               std::vector<std::pair<const void*, int>>* cols);
   void maybe_compact_merge();
   void purge(int64_t wm);
   void zero_panes(int64_t r, int64_t k);
@@ -382,6 +392,11 @@ class WindowStep {
   Buf chk_, hchk_;
   Buf out_keys_, out_vals_, out_raw_, out_cnt_, fire_bounds_, hbounds_, out_vec_;
   Buf stage_[5];
+  // Top-N cut (cfg_.top_n > 0): candidate columns + bounds + select scratch. Written after the
+  // fire kernels on the same stream and read by the same counted copy as the flags, so
+  // out_busy_ / claim_flags() guard them together with out_* and stage_*.
+  Buf top_keys_, top_vals_, top_raw_, top_cnt_, top_bounds_, top_scratch_;
+  int top_src_ = 0;
   Buf rout_[10];
   int64_t rout_cap_ = 0;
   bool rout_kv_ = false;

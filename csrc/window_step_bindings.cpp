@@ -164,6 +164,8 @@ WindowStepConfig make_cfg(py::dict d) {
   c.emit_kv = get("emit_kv").cast<bool>();
   c.latency_fire = get("latency_fire").cast<int>();
   c.window_keys = get("window_keys").cast<int64_t>();
+  if (d.contains("top_n")) c.top_n = get("top_n").cast<int64_t>();
+  if (d.contains("top_smallest")) c.top_smallest = get("top_smallest").cast<bool>();
   c.dim = get("dim").cast<int>();
   c.vec_avg = get("vec_avg").cast<bool>();
   c.vec_has_threshold = !get("vec_threshold").is_none();
@@ -227,6 +229,7 @@ py::dict metrics_dict(const StepMetrics& m) {
   put("dropped_keys", m.dropped_keys);
   put("spilled_keys", m.spilled_keys);
   put("spilled_rows", m.spilled_rows);
+  put("topn_rows_in", m.topn_rows_in);
   d["extra"] = x;
   return d;
 }

@@ -204,3 +204,49 @@ class WindowQuantiles(ProcessWindowFunction):
             values.sort()
         n = len(values)
         out.collect(Tuple([key] + [values[quantile_rank(n, p)] if n else 0.0 for p in self.ppm]))
+
+
+class WindowTopN(ProcessWindowFunction):
+    """The n elements of a ``window_all`` window with the largest (``largest=False``: smallest)
+    value in `field`, emitted unchanged in rank order -- "which 10 hosts used the most bandwidth
+    this minute" as ``key_by(host).time_window(..).sum(bytes)`` followed by
+    ``time_window_all(..).process(WindowTopN(1, 10))``.
+
+    Order: by `field` (integers by value, doubles in Java ``Double.compare`` order: -0.0 < 0.0,
+    NaN largest), best first; equal values by `tie_field` ascending in the natural order of the
+    Python object (``int``, or ``str``); then by arrival. ``rank`` is that order and this method
+    the exact host implementation. ``native`` lets the planner fold the cut into the keyed
+    window operator upstream (its ``top_n``): the device then emits only the rows at or above
+    the n-th best value of each firing -- every row that ties there included, so the device
+    never breaks a tie -- and the operator applies ``rank`` to those candidates."""
+
+    def __init__(self, field: int, n: int, largest: bool = True, tie_field: int = 0):
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"WindowTopN: n is an int >= 1, got {n!r}")
+        for name, f in (("field", field), ("tie_field", tie_field)):
+            if isinstance(f, bool) or not isinstance(f, int) or f < 0:
+                raise ValueError(f"WindowTopN: {name} is a non-negative int, got {f!r}")
+        if field == tie_field:
+            raise ValueError("WindowTopN: field and tie_field must differ")
+        self.field, self.n, self.largest, self.tie_field = field, n, bool(largest), tie_field
+        self.native = ("topn", field, n, self.largest, tie_field)
+
+    def rank(self, elements) -> list:
+        """The first n of `elements` in rank order."""
+        elems = list(elements)
+        vals = [e[self.field] for e in elems]
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f"WindowTopN: field {self.field} must be numeric, got {v!r}")
+        if all(isinstance(v, int) for v in vals):
+            words = vals
+        else:
+            words = [_double_order(float(v)) for v in vals]
+        sign = -1 if self.largest else 1
+        order = sorted(range(len(elems)),
+                       key=lambda i: (sign * words[i], elems[i][self.tie_field], i))
+        return [elems[i] for i in order[:self.n]]
+
+    def process(self, key, context, elements, out):
+        for e in self.rank(elements):
+            out.collect(e)

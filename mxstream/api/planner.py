@@ -12,6 +12,9 @@ runs:
   * keep-first fields other than the key are dead: the only consumer is a map whose traced
     output reads just the key and the aggregate (BandwidthMonitorWithEventTime.java:48-53),
     or the tuple has no such fields.
+
+A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
+(``_lower_topn``): the keyed operator cuts each firing to its top-N candidates on the device.
 """
 from __future__ import annotations
 
@@ -340,7 +343,77 @@ def plan(env, sinks):
                         session=session)
         if not session and kind in ("sum", "min", "max") and result == "tuple":
             _fuse_window_epilogue(env, t, children, key_pos, val_pos, ok_arities)
+        if not session and t.meta.get("native") and kind in ("sum", "min", "max", "count", "avg"):
+            t.meta = dict(t.meta, reduce_kind=kind, key_pos=key_pos, val_pos=val_pos,
+                          scalar=result == "value")
+    _lower_topn(env, nodes, children)
     return sinks
+
+
+def _lower_topn(env, nodes, children) -> None:
+    """keyed window (native sum / min / max / count / avg, epilogue fused or not) ->
+    ``window_all(tumbling).process(WindowTopN)``: when every all-window holds exactly one firing
+    of the keyed window, the keyed operator cuts each firing to its top-N candidates on the
+    device (KeyedWindowOperator top_n), ranks them with the function and emits what the
+    all-window operator would have; that node becomes a pass-through. Anything else -- lateness
+    or a late tag on either window, another trigger / evictor / assigner, a size that is not the
+    keyed window's slide, a second consumer, more than one rank -- keeps the host operators."""
+    from ..runtime.columnar import PassThroughOp
+
+    comm = getattr(env, "_comm", None)
+    if (comm.world if comm is not None else getattr(env, "world", 1)) > 1:
+        return
+    for t in nodes:
+        meta = getattr(t, "meta", None) or {}
+        if meta.get("kind") != "window" or meta.get("fused"):
+            continue
+        ws, spec = meta["stream"], meta["spec"]
+        fn = spec.fn
+        if ws.keyed is not None or type(ws.assigner) is not W.TumblingEventTimeWindows \
+                or ws._trigger is not None or ws._evictor is not None or ws._lateness \
+                or ws._late_tag is not None or spec.kind != "process" \
+                or getattr(fn, "native", (None,))[0] != "topn" or len(t.parents) != 1:
+            continue
+        # up through the map / filter nodes the keyed window fused into its fire kernel
+        p = t.parents[0]
+        while True:
+            pm = getattr(p, "meta", None) or {}
+            if pm.get("fused") and pm.get("kind") in ("map", "filter") and len(p.parents) == 1 \
+                    and len(children[p.id]) == 1:
+                p = p.parents[0]
+                continue
+            break
+        if pm.get("kind") != "window" or not pm.get("native") or "reduce_kind" not in pm \
+                or len(children[p.id]) != 1 or pm.get("scalar") or pm.get("fused_scalar"):
+            continue
+        pws = pm["stream"]
+        pa, a = pws.assigner, ws.assigner
+        if not isinstance(pa, (W.TumblingEventTimeWindows, W.SlidingEventTimeWindows)) \
+                or pws._lateness or pws._late_tag is not None:
+            continue
+        # one upstream firing per all-window: its rows carry window_end - 1
+        if a.size != pa.slide or (pa.offset + pa.size - a.offset) % a.size:
+            continue
+        layout = pm.get("fused_layout")
+        if layout is None:
+            ok = fn.field == pm["val_pos"] and fn.tie_field == pm["key_pos"]
+        else:
+            want = -1 if pm.get("fused_map") else pm["val_pos"]
+            ok = (max(fn.field, fn.tie_field) < len(layout) and layout[fn.field] == want
+                  and layout[fn.tie_field] == pm["key_pos"] and pm["key_pos"] != pm["val_pos"])
+        if not ok:
+            continue
+        inner, tail = p.factory, t.factory
+
+        def factory(inner=inner, fn=fn, tail=tail):
+            op = inner()
+            op.top_fn, op.top_tail_factory = fn, tail
+            return op
+
+        p.factory = factory
+        p.meta = dict(pm, top_n=fn.n)
+        t.factory = PassThroughOp
+        t.meta = dict(meta, fused=True)
 
 
 def _count_window_size(ws) -> int | None:
@@ -517,6 +590,8 @@ def _fuse_window_epilogue(env, t, children, key_pos: int, val_pos: int, ok_ariti
         return op
 
     t.factory = factory
+    t.meta = dict(t.meta, fused_layout=None if scalar else tuple(layout), fused_scalar=scalar,
+                  fused_map=bool(exprs))
     m.factory = PassThroughOp
     m.meta = dict(mmeta, fused=True)
     if fnode is not None:

@@ -920,9 +920,91 @@ def config7(lines: int = 16_000_000, channels: int = 1_000, device: str = "cuda"
             "ingest": "device" if str(device).startswith("cuda") else "host", "device": device}
 
 
+def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_000,
+             device: str = "cuda", top_n: int | None = None, n: int = 10) -> dict:
+    """Top-N hosts by bytes per minute at the headline shape: 1M dense keys, 1-min tumbling
+    event-time int64 sum, device-generated events, then the N keys with the largest sums of
+    every firing. top_n = N: the operator cuts each firing to its candidates on the device
+    (KeyedWindowOperator top_n) and the host ranks those; None: the firing leaves in full (one
+    28-byte row per key) and numpy takes the top N on the host -- what the same query costs
+    without the cut. Both print the same winners (`top_checksum`)."""
+    dev = torch.device("cuda", 0) if device != "cpu" and torch.cuda.is_available() \
+        else torch.device("cpu")
+    step_ms, disorder = 5_000, 2_000
+    op = KeyedWindowOperator(size=60_000, agg=K.AGG_SUM_I64, device=dev, max_keys=keys,
+                             batch_capacity=batch, ooo_bound=disorder, dense_keys=True,
+                             pipeline="stream", **({} if top_n is None else {"top_n": top_n}))
+    want = n if top_n is None else top_n
+    k = torch.empty(batch, dtype=torch.int64, device=dev)
+    ts = torch.empty_like(k)
+    vals = torch.empty_like(k)
+    t0_event = 1_566_957_600_000
+    state = {"i": 0, "check": 0, "windows": 0}
+    lat: list[float] = []
+
+    def rank(fr) -> None:
+        """The window's top rows: sum descending, key ascending (api/aggregations.WindowTopN)."""
+        raw = fr.raw.view(np.int64) if fr.raw.dtype == np.uint64 else fr.raw
+        keys_ = fr.keys.view(np.int64) if fr.keys.dtype == np.uint64 else fr.keys
+        if raw.size > want:
+            thr = np.partition(raw, raw.size - want)[raw.size - want]
+            sel = np.nonzero(raw >= thr)[0]
+        else:
+            sel = np.arange(raw.size)
+        order = sel[np.lexsort((keys_[sel], -raw[sel]))][:want]
+        state["check"] = (state["check"] * 31 + int(keys_[order].sum()) * 7 + int(raw[order].sum())) % (1 << 61)
+        state["windows"] += 1
+
+    def step(drain: bool = False):
+        i = state["i"]
+        t_in = time.perf_counter()
+        if drain:
+            fired = op.flush()
+        else:
+            K.gen_events(k, ts, vals, seed=1234, stream_id=0, idx0=i * batch, nkeys=keys,
+                         ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=disorder,
+                         val_lo=0, val_span=20_000)
+            fired = op.process(k, ts, vals)
+            state["i"] = i + 1
+        for fr in fired:
+            rank(fr)
+        if fired:
+            lat.append((time.perf_counter() - t_in) * 1e3)
+
+    for _ in range(warmup):
+        step()
+    _sync(dev)
+    lat.clear()
+    out0, fires0 = op.metrics.num_records_out, state["windows"]
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    step(drain=True)
+    _sync(dev)
+    dt = time.perf_counter() - t0
+    fires = state["windows"] - fires0
+    rows = op.metrics.num_records_out - out0
+    return {"config": 10, "metric": "events/sec (top-N keys of a 1-min tumbling sum, "
+                                    + ("device cut)" if top_n is not None else "host cut)"),
+            "value": batch * steps / dt, "unit": "events/s", "ms_per_step": dt / steps * 1e3,
+            "p50_fire_step_ms": statistics.median(lat) if lat else None,
+            "firings_measured": fires, "top_n": want,
+            "cut": "device" if top_n is not None else "host",
+            "d2h_rows_per_firing": rows / fires if fires else None,
+            "d2h_bytes_per_firing": rows * 28 / fires if fires else None,
+            "fired_rows_per_firing": (op.metrics.extra.get("topn_rows_in", 0) / op.metrics.num_fires
+                                      if top_n is not None and op.metrics.num_fires else
+                                      (rows / fires if fires else None)),
+            "top_checksum": state["check"], "keys": keys, "events_per_step": batch,
+            "device": str(dev)}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10])
+    ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
+                    help="config 10: cut every firing to its top N on the device (default N = "
+                         "10); without it the firing leaves in full and numpy takes the top 10")
     ap.add_argument("--dim", type=int, default=32, help="config 6: metric vector width")
     ap.add_argument("--valu", action="store_true", help="config 6: VALU instead of MFMA reduce")
     ap.add_argument("--zipf", type=float, default=0.0, help="config 6: power-law key skew")
@@ -982,6 +1064,9 @@ def main(argv=None) -> int:
     elif a.config == 8:
         r = config8(a.steps, a.warmup, a.batch or (1 << 22), device=a.device,
                     quantiles=[float(x) for x in a.quantiles.split(",")] if a.quantiles else None)
+    elif a.config == 10:
+        r = config10(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 1_000_000,
+                     device=a.device, top_n=a.top_n)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

@@ -555,3 +555,67 @@ def segment_quantiles(heads: torch.Tensor, ord_bits: torch.Tensor, ppm) -> torch
     else:
         m.cpu_segment_quantile_select(*args)
     return out
+
+
+TOPN_SOURCES = {"value": 0, "raw": 1, "count": 2}  # csrc/mxs_common.h TopSrc
+
+
+def topn_source(agg: int, has_map: bool) -> str:
+    """The order-word source of a window operator's top-N cut (csrc/mxs_common.h topn_source)."""
+    code = load().topn_source(int(agg), bool(has_map))
+    return next(k for k, v in TOPN_SOURCES.items() if v == code)
+
+
+def topn_select(keys: torch.Tensor, vals: torch.Tensor, raw: torch.Tensor | None,
+                cnt: torch.Tensor | None, bounds: torch.Tensor, *, n: int, source: str = "value",
+                smallest: bool = False):
+    """Top-N candidates of fired windows, cut on the input's device without a host read.
+
+    The columns hold ``bounds.numel()`` windows back to back; ``bounds[w]`` (int32, device) = rows
+    of windows 0..w, rows past the columns' length do not exist. keys: int64, or int32 (the
+    ``emit="key_value"`` layout); vals: float64; raw (int64) / cnt (int32) may be None unless
+    they are the order `source` ("value": Double.compare order of vals, "raw": signed int64,
+    "count"). A window's candidates are its rows whose order word is >= its n-th largest (with
+    `smallest`: <= its n-th smallest) -- every row tying at the threshold included, all rows of a
+    window with <= n rows. Returns (keys, vals, raw, cnt, out_bounds): columns of the inputs'
+    capacity holding the candidates contiguous in window order (any order inside a window) and
+    their cumulative bounds."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("topn_select: n must be an int >= 1")
+    if source not in TOPN_SOURCES:
+        raise ValueError(f"topn_select: source must be one of {sorted(TOPN_SOURCES)}")
+    dev = keys.device
+    key32 = keys.dtype == torch.int32
+    cap = keys.numel()
+    nwin = bounds.numel()
+    m = load()
+    _check(keys, torch.int32 if key32 else torch.int64, cap, "keys", dev)
+    _check(vals, torch.float64, cap, "vals", dev)
+    if raw is not None:
+        _check(raw, torch.int64, cap, "raw", dev)
+    if cnt is not None:
+        _check(cnt, torch.int32, cap, "cnt", dev)
+    _check(bounds, torch.int32, nwin, "bounds", dev)
+    if source == "raw" and raw is None:
+        raise ValueError("topn_select: source 'raw' needs the raw column")
+    if source == "count" and cnt is None:
+        raise ValueError("topn_select: source 'count' needs the cnt column")
+    if nwin > m.TOPN_MAX_WIN:
+        raise ValueError(f"topn_select: at most {m.TOPN_MAX_WIN} windows a call")
+    if cap >= 1 << 32:
+        raise ValueError("topn_select: columns must hold fewer than 2^32 rows")
+    okeys, ovals = torch.empty_like(keys), torch.empty_like(vals)
+    oraw = None if raw is None else torch.empty_like(raw)
+    ocnt = None if cnt is None else torch.empty_like(cnt)
+    obounds = torch.zeros_like(bounds)
+    if nwin == 0:
+        return okeys, ovals, oraw, ocnt, obounds
+    cols = (_p(keys), _p(vals), _p(raw), _p(cnt))
+    out = (_p(okeys), _p(ovals), _p(oraw), _p(ocnt))
+    plan = (TOPN_SOURCES[source], bool(smallest), key32, nwin, min(n, 1 << 62), cap)
+    if _is_gpu(keys):
+        scratch = torch.empty(m.topn_scratch_bytes(nwin) // 4, dtype=torch.int32, device=dev)
+        m.gpu_topn_select(cols, _p(bounds), plan, out, _p(obounds), _p(scratch), _stream(keys))
+    else:
+        m.cpu_topn_select(cols, _p(bounds), plan, out, _p(obounds))
+    return okeys, ovals, oraw, ocnt, obounds

@@ -130,6 +130,42 @@ class _ColumnInput:
                            cat([b.sub for b in batches]))
 
 
+class _ChainedOps(Operator):
+    """Two host operators run back to back as one (the second consumes what the first emits)."""
+
+    def __init__(self, first: Operator, second: Operator):
+        self.first, self.second = first, second
+
+    def open(self, ctx):
+        super().open(ctx)
+        self.first.open(ctx)
+        self.second.open(ctx)
+
+    def process(self, items):
+        return self.second.process(self.first.process(items))
+
+    def on_processing_time(self, now):
+        return self.second.process(self.first.on_processing_time(now)) + \
+            self.second.on_processing_time(now)
+
+    def finish(self):
+        return self.second.process(self.first.finish()) + self.second.finish()
+
+    def close(self):
+        self.first.close()
+        self.second.close()
+
+    def take_side(self, tag_id):
+        return self.first.take_side(tag_id) + self.second.take_side(tag_id)
+
+    def snapshot(self) -> dict:
+        return {"first": self.first.snapshot(), "second": self.second.snapshot()}
+
+    def restore(self, snap: dict) -> None:
+        self.first.restore(snap["first"])
+        self.second.restore(snap["second"])
+
+
 class NativeWindowOp(_ColumnInput, Operator):
     name = "Window(native)"
     accepts_columns = True
@@ -312,8 +348,21 @@ class NativeWindowOp(_ColumnInput, Operator):
             side_output_late=self.late_tag is not None, clock=self.ctx.clock,
             dense_keys=dense, map_prog=self.map_prog or E.EMPTY,
             filter_prog=self.filter_prog or E.EMPTY,
-            emit="key_value" if self._key_value_only() else "full")
+            emit="key_value" if self._key_value_only() else "full", **self._top_args(multi))
         return True
+
+    # A downstream ``window_all(..).process(WindowTopN)`` folded into this operator
+    # (planner._lower_topn): the engine cuts every firing to its candidates on the device
+    # (KeyedWindowOperator top_n) and _emit ranks them with the function itself.
+    top_fn = None            # the WindowTopN
+    top_tail_factory = None  # the host all-window operator, for the fallback path
+
+    def _top_args(self, multi: bool) -> dict:
+        """The engine's cut, where it can run (the spill tier and G > 1 fire through paths
+        without one: their firings leave in full and _emit ranks all rows)."""
+        if self.top_fn is None or self._spill_state or multi:
+            return {}
+        return {"top_n": self.top_fn.n, "top_order": "largest" if self.top_fn.largest else "smallest"}
 
     def _key_value_only(self) -> bool:
         """The output tuple reads only the key and the mapped value (no raw result, count or
@@ -325,6 +374,9 @@ class NativeWindowOp(_ColumnInput, Operator):
 
     def _to_fallback(self):
         self.fallback = self.fallback_factory()
+        if self.top_tail_factory is not None:
+            # the all-window node downstream is a pass-through: its host operator runs here
+            self.fallback = _ChainedOps(self.fallback, self.top_tail_factory())
         self.fallback.open(self.ctx)
 
     def _key_id(self, k) -> int:
@@ -574,9 +626,20 @@ class NativeWindowOp(_ColumnInput, Operator):
                             ts, self._subtasks(keys), scalar)]
 
     def _emit(self, fired) -> list:
+        if self.top_fn is not None:
+            # Per window: the candidates as the records the host path would see, ranked and cut
+            # by the function; emitted like the all-window operator's output (subtask 0).
+            out = []
+            for fr in fired:
+                values = [r.value for r in self._emit_records([fr])]
+                out.extend(Rec(v, fr.window_end - 1, 0) for v in self.top_fn.rank(values))
+            return out
         kinds = self._columnar_kinds() if fired else None
         if kinds is not None:
             return self._emit_columns(fired, kinds)
+        return self._emit_records(fired)
+
+    def _emit_records(self, fired) -> list:
         out = []
         P, MP = self.ctx.parallelism, self.ctx.max_parallelism
         for fr in fired:

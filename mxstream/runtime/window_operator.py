@@ -149,7 +149,8 @@ class KeyedWindowOperator(_StateMixin):
                  idle_timeout_steps: int | None = None, deterministic: bool = False,
                  spill: bool = False, spill_load: float = 0.8, spill_check_steps: int = 8,
                  spill_keep_panes: int | None = None, emit: str = "full",
-                 latency_fire: int = 0, window_keys: int | None = None, _vector: dict | None = None):
+                 latency_fire: int = 0, window_keys: int | None = None, _vector: dict | None = None,
+                 top_n: int | None = None, top_order: str = "largest"):
         """deterministic: f64 sums/averages accumulate each step's per-slot sum in 128-bit fixed
         point (order-independent integer adds, one rounding per slot and step), so results are
         bit-identical between runs, between the GPU and the C++ twin, and independent of the
@@ -176,9 +177,22 @@ class KeyedWindowOperator(_StateMixin):
         spill: host-DRAM tier for hashed keys. Every `spill_check_steps` steps, a sub-table above
         `spill_load` of its slots triggers window_compact: keys without live data are dropped,
         keys whose newest data pane is older than the newest `spill_keep_panes` panes (default:
-        one window) move to the tier."""
+        one window) move to the tier.
+
+        top_n = N: every firing is cut on the device to its top-N candidates -- the rows whose
+        order word is >= the window's N-th largest (top_order="smallest": <= its N-th smallest).
+        The order word is the raw accumulator of an integer sum / min / max without a map
+        program, the count of a count aggregate, else the mapped value in Double.compare order.
+        Rows that tie at the threshold all leave, so a FireResult holds >= min(rows, N) rows in
+        no particular order: the consumer sorts and settles ties (api/aggregations.py
+        WindowTopN). One rank, no lateness, late side output, spill or vector windows.
+        ``metrics.extra["topn_rows_in"]`` counts the rows the fire kernels produced."""
         if emit not in ("full", "key_value"):
             raise ValueError("emit must be 'full' or 'key_value'")
+        if top_order not in ("largest", "smallest"):
+            raise ValueError("top_order must be 'largest' or 'smallest'")
+        if top_n is not None and (isinstance(top_n, bool) or not isinstance(top_n, int) or top_n < 1):
+            raise ValueError("top_n must be an int >= 1")
         if time_mode not in ("event", "processing"):
             raise ValueError("time_mode must be 'event' or 'processing'")
         if exchange not in ("auto", "records", "partials"):
@@ -202,6 +216,7 @@ class KeyedWindowOperator(_StateMixin):
         self.latency_fire = max(0, int(latency_fire))
         self.deterministic = bool(deterministic) and agg in (K.AGG_SUM_F64, K.AGG_AVG_F64)
         self.spill_keep_panes = spill_keep_panes
+        self.top_n, self.top_order = top_n, top_order
         vec = _vector or {}
         cuda = self.device.type == "cuda"
         cfg = dict(
@@ -226,6 +241,7 @@ class KeyedWindowOperator(_StateMixin):
             spill_keep_panes=-1 if spill_keep_panes is None else int(spill_keep_panes),
             emit_kv=emit == "key_value", latency_fire=self.latency_fire,
             window_keys=-1 if window_keys is None else int(window_keys),
+            top_n=0 if top_n is None else min(top_n, 1 << 62), top_smallest=top_order == "smallest",
             dim=int(vec.get("dim", 0)), vec_avg=bool(vec.get("avg", True)),
             vec_threshold=vec.get("threshold"), vec_mode=int(vec.get("mode", 0)))
         from ..ops.native import load
