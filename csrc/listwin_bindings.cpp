@@ -136,4 +136,32 @@ void bind_listwin(py::module_& m) {
     else
       cpu::lw_key_scatter(w, kmin, LP<int64_t>(cursor), LP<uint64_t>(out_ord));
   });
+  // Distinct words per segment (mxs_listwin.h): the two device passes and the sorting twin. The
+  // caller (ops/kernels.py segment_distinct_launch) owns the list, the meta words and the scratch.
+  m.attr("DISTINCT_LDS") = kDistinctLds;
+  m.attr("DISTINCT_WORD_BITS") = kDistinctWordBits;
+  m.attr("DISTINCT_ENTRY") = kDistinctEntry;
+  m.attr("DISTINCT_META") = kDistinctMeta;
+  m.attr("DISTINCT_ERR") = kDistinctErr;
+  m.def("gpu_segment_distinct_short", [](intptr_t heads, int64_t nseg, int64_t total, intptr_t ord,
+                                         intptr_t out, intptr_t list, int64_t list_cap,
+                                         intptr_t meta, intptr_t stream) {
+    gpu::segment_distinct_short(LP<int64_t>(heads), nseg, total, LP<uint64_t>(ord),
+                                LP<int64_t>(out), LP<int64_t>(list), list_cap, LP<int64_t>(meta),
+                                stream);
+  });
+  m.def("gpu_segment_distinct_long", [](intptr_t heads, int64_t nseg, int64_t total, intptr_t ord,
+                                        intptr_t list, int64_t n_long, int64_t long_elems,
+                                        intptr_t scratch, intptr_t out, intptr_t meta,
+                                        intptr_t stream) {
+    gpu::segment_distinct_long(LP<int64_t>(heads), nseg, total, LP<uint64_t>(ord),
+                               LP<int64_t>(list), n_long, long_elems, LP<uint64_t>(scratch),
+                               LP<int64_t>(out), LP<int64_t>(meta), stream);
+  });
+  m.def("cpu_segment_distinct_count", [](intptr_t heads, int64_t nseg, int64_t total, intptr_t ord,
+                                         intptr_t out) {
+    py::gil_scoped_release nogil;
+    cpu::segment_distinct_count(LP<int64_t>(heads), nseg, total, LP<uint64_t>(ord),
+                                LP<int64_t>(out));
+  });
 }

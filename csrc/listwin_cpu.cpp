@@ -1,7 +1,9 @@
 // mxstream — C++ twins of the list-window (process window) kernels (csrc/listwin_hip.hip):
 // the same pane arena and counting-sort firing on the host, for the CPU engine and the
 // differential tests.
+#include <algorithm>
 #include <stdexcept>
+#include <vector>
 
 #include "mxs_listwin.h"
 
@@ -82,6 +84,23 @@ void lw_rank_scatter(const LwRankPanes& w, int64_t kmin, int64_t nkeys, const in
       out_ord[offs[k] + pre[(int64_t)j * nkeys + k] + w.p[j].ranks[i]] =
           f64_order_bits(w.p[j].vals[i]);
     }
+}
+
+void segment_distinct_count(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
+                            int64_t* out) {
+  std::vector<uint64_t> v;
+  for (int64_t s = 0; s < nseg; ++s) {
+    const int64_t a = heads[s], e = s + 1 < nseg ? heads[s + 1] : total;
+    if (e <= a) {
+      out[s] = 0;
+      continue;
+    }
+    v.assign(ord + a, ord + e);
+    std::sort(v.begin(), v.end());
+    int64_t d = 1;
+    for (size_t i = 1; i < v.size(); ++i) d += v[i] != v[i - 1];
+    out[s] = d;
+  }
 }
 
 }  // namespace cpu

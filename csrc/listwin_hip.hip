@@ -7,7 +7,8 @@
 // elements per dense key id, scans the counts (order-preserving, so segments come out in key
 // order) and scatters the values into their key segments as order bits; the per-segment median
 // selection (segment_median_select, csrc/kernels_hip.hip) never needs a comparison sort of the
-// whole window.
+// whole window. func "distinct" counts the different words of every segment instead
+// (segment_distinct_short / segment_distinct_long below: hash sets in LDS and in a device scratch).
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
@@ -288,6 +289,177 @@ __global__ __launch_bounds__(kScanThreads) void lw_tile_write_kernel(
   }
 }
 
+// ---- distinct count of every segment (func "distinct") -------------------------------------
+// The slot of word x in a table of `cap` (power of two) slots is the top log2(cap) bits of
+// mix64(x) (bijective, so different words differ somewhere in the mixed word); in a table of
+// any size m it is mulhi(mix64(x), m). Tables are at most half full, so linear probing ends;
+// the loops are bounded by the table size all the same and report a hit bound in
+// meta[kDistinctErr].
+__device__ __forceinline__ void lw_wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// One wave per segment, four per workgroup (the median kernel's layout and LDS budget: 4 x 2048
+// words). The wave clears cap = max(128, next_pow2(2n)) slots, every lane reads its words from
+// global memory once and claims a slot with a 64-bit LDS compare-and-swap: old value empty =
+// claimed (a new word), old value x = duplicate, anything else = next slot. A segment of more
+// than kDistinctLds words is only listed here (one atomic reserves its list entry and its 2n
+// scratch words) and counted by segment_distinct_long_kernel.
+__global__ __launch_bounds__(256) void segment_distinct_short_kernel(
+    const int64_t* __restrict__ heads, int64_t nseg, int64_t total,
+    const uint64_t* __restrict__ ord, int64_t* __restrict__ out, int64_t* __restrict__ list,
+    int64_t list_cap, int64_t* __restrict__ meta) {
+  __shared__ unsigned long long tab[4][2 * kDistinctLds];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned long long* t = tab[w];
+  for (int64_t s = (int64_t)blockIdx.x * 4 + w; s < nseg; s += (int64_t)gridDim.x * 4) {
+    const int64_t a = heads[s], e = s + 1 < nseg ? heads[s + 1] : total;
+    const int64_t n = e - a;
+    if (n <= 0) {
+      if (lane == 0) out[s] = 0;
+      continue;
+    }
+    if (n > kDistinctLds) {
+      if (lane == 0) {
+        out[s] = 0;
+        const unsigned long long c =
+            atomicAdd((unsigned long long*)&meta[kDistinctCursor],
+                      (1ull << kDistinctWordBits) + 2ull * (unsigned long long)n);
+        const int64_t idx = (int64_t)(c >> kDistinctWordBits);
+        if (idx < list_cap) {
+          list[idx * kDistinctEntry] = s;
+          list[idx * kDistinctEntry + 1] = (int64_t)(c & ((1ull << kDistinctWordBits) - 1ull));
+        } else {
+          meta[kDistinctErr] = 2;
+        }
+      }
+      continue;
+    }
+    int cap = 128;
+    while (cap < 2 * (int)n) cap <<= 1;
+    const int shift = 33 + __clz(cap);  // 64 - log2(cap)
+    for (int i = lane; i < cap; i += 64) t[i] = kDistinctEmpty;
+    lw_wave_lds_sync();
+    uint32_t claims = 0;
+    bool saw_empty = false, spun = false;
+    // Four independent loads per lane in flight before the first insert (a word past the end
+    // reads as the empty marker without counting as one).
+    for (int i0 = lane; i0 < (int)n; i0 += 4 * 64) {
+      unsigned long long x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * 64;
+        x[u] = i < (int)n ? ord[a + i] : (unsigned long long)kDistinctEmpty;
+        saw_empty = saw_empty || (i < (int)n && x[u] == kDistinctEmpty);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (x[u] == kDistinctEmpty) continue;
+        int slot = (int)(mix64(x[u]) >> shift);
+        int probes = 0;
+        for (; probes < cap; ++probes) {
+          const unsigned long long old =
+              atomicCAS(&t[slot], (unsigned long long)kDistinctEmpty, x[u]);
+          if (old == kDistinctEmpty) {
+            ++claims;
+            break;
+          }
+          if (old == x[u]) break;
+          slot = (slot + 1) & (cap - 1);
+        }
+        spun = spun || probes == cap;
+      }
+    }
+    for (int o = 32; o >= 1; o >>= 1) claims += __shfl_xor(claims, o);
+    const bool any_empty = __ballot(saw_empty) != 0ull, any_spun = __ballot(spun) != 0ull;
+    if (lane == 0) {
+      out[s] = (int64_t)claims + (any_empty ? 1 : 0);
+      if (any_spun) meta[kDistinctErr] = 1;
+    }
+    lw_wave_lds_sync();  // every lane is done with the table before the next segment clears it
+  }
+}
+
+// The listed long segments, laid end to end in list order (entry j starts at element base_j / 2:
+// the short pass reserved 2n words per segment with one atomic, so bases ascend with j). Every
+// workgroup takes tiles of kDistinctTile of those elements, so one hot key's segment is spread
+// over many workgroups that insert into the same table with 64-bit global compare-and-swap; a
+// relaxed load first keeps duplicates (the common case of a hot key) off the atomic unit -- a
+// slot only ever goes from empty to one word, so a value seen there is final. Claims are summed
+// per workgroup and added to out[s] with one atomic; the first workgroup to flag that it saw
+// the empty marker adds one for it.
+__global__ __launch_bounds__(256) void segment_distinct_long_kernel(
+    const int64_t* __restrict__ heads, int64_t nseg, int64_t total,
+    const uint64_t* __restrict__ ord, int64_t* __restrict__ list, int64_t n_long,
+    int64_t long_elems, uint64_t* __restrict__ scratch, int64_t* __restrict__ out,
+    int64_t* __restrict__ meta) {
+  __shared__ uint32_t wsum[4], wflag[4];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int64_t t0 = (int64_t)blockIdx.x * kDistinctTile; t0 < long_elems;
+       t0 += (int64_t)gridDim.x * kDistinctTile) {
+    const int64_t t1 = t0 + kDistinctTile < long_elems ? t0 + kDistinctTile : long_elems;
+    // the last entry that starts at or before t0 (entry 0 starts at 0)
+    int64_t lo = 0, hi = n_long;
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((list[mid * kDistinctEntry + 1] >> 1) <= t0) lo = mid; else hi = mid;
+    }
+    for (int64_t j = lo; j < n_long; ++j) {
+      const int64_t s = list[j * kDistinctEntry], base = list[j * kDistinctEntry + 1];
+      const int64_t e0 = base >> 1;
+      if (e0 >= t1) break;
+      const int64_t a = heads[s], n = (s + 1 < nseg ? heads[s + 1] : total) - a;
+      const int64_t b = (t0 > e0 ? t0 : e0) - e0, e = (t1 < e0 + n ? t1 : e0 + n) - e0;
+      const uint64_t m = 2ull * (uint64_t)n;
+      unsigned long long* tb = reinterpret_cast<unsigned long long*>(scratch + base);
+      uint32_t claims = 0;
+      bool saw_empty = false, spun = false;
+      for (int64_t i = b + threadIdx.x; i < e; i += 256) {
+        const unsigned long long x = ord[a + i];
+        if (x == kDistinctEmpty) {
+          saw_empty = true;
+          continue;
+        }
+        uint64_t slot = __umul64hi(mix64(x), m);
+        uint64_t probes = 0;
+        for (; probes < m; ++probes) {
+          unsigned long long old =
+              __hip_atomic_load(&tb[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (old == kDistinctEmpty) {
+            old = atomicCAS(&tb[slot], (unsigned long long)kDistinctEmpty, x);
+            if (old == kDistinctEmpty) {
+              ++claims;
+              break;
+            }
+          }
+          if (old == x) break;
+          slot = slot + 1 == m ? 0 : slot + 1;
+        }
+        spun = spun || probes == m;
+      }
+      for (int o = 32; o >= 1; o >>= 1) claims += __shfl_xor(claims, o);
+      const bool any_empty = __ballot(saw_empty) != 0ull, any_spun = __ballot(spun) != 0ull;
+      if (lane == 0) {
+        wsum[w] = claims;
+        wflag[w] = (any_empty ? 1u : 0u) | (any_spun ? 2u : 0u);
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        unsigned long long sum = (unsigned long long)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        const uint32_t f = wflag[0] | wflag[1] | wflag[2] | wflag[3];
+        if ((f & 1u) &&
+            atomicCAS((unsigned long long*)&list[j * kDistinctEntry + 2], 0ull, 1ull) == 0ull)
+          ++sum;
+        if (sum) atomicAdd((unsigned long long*)&out[s], sum);
+        if (f & 2u) meta[kDistinctErr] = 1;
+      }
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace
 
 namespace gpu {
@@ -379,6 +551,31 @@ void lw_rank_scatter(const LwRankPanes& w, int64_t kmin, int64_t nkeys, const in
   if (mx <= 0) return;
   hipLaunchKernelGGL(lw_rank_scatter_kernel, dim3(grid_of(mx, kLwBlock * 8, 4096), w.n),
                      dim3(kLwBlock), 0, (hipStream_t)stream, w, kmin, nkeys, offs, pre, out_ord);
+  LW_CHECK(hipGetLastError());
+}
+
+void segment_distinct_short(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
+                            int64_t* out, int64_t* list, int64_t list_cap, int64_t* meta,
+                            intptr_t stream) {
+  if (total < 0 || total >= (1ll << (kDistinctWordBits - 2)))
+    throw std::invalid_argument("segment_distinct: total out of range");
+  if (list_cap < total / (kDistinctLds + 1))
+    throw std::invalid_argument("segment_distinct: list shorter than total / 1025 entries");
+  if (nseg <= 0) return;
+  hipLaunchKernelGGL(segment_distinct_short_kernel, dim3(grid_of(nseg, 4, 16384)), dim3(256), 0,
+                     (hipStream_t)stream, heads, nseg, total, ord, out, list, list_cap, meta);
+  LW_CHECK(hipGetLastError());
+}
+
+void segment_distinct_long(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
+                           int64_t* list, int64_t n_long, int64_t long_elems, uint64_t* scratch,
+                           int64_t* out, int64_t* meta, intptr_t stream) {
+  if (n_long <= 0 || long_elems <= 0) return;
+  if (n_long > nseg || long_elems > total || long_elems < n_long * (int64_t)(kDistinctLds + 1))
+    throw std::invalid_argument("segment_distinct: long-segment counts out of range");
+  hipLaunchKernelGGL(segment_distinct_long_kernel, dim3(grid_of(long_elems, kDistinctTile, 8192)),
+                     dim3(256), 0, (hipStream_t)stream, heads, nseg, total, ord, list, n_long,
+                     long_elems, scratch, out, meta);
   LW_CHECK(hipGetLastError());
 }
 

@@ -11,6 +11,16 @@
 //   lw_scan          counts -> exclusive offsets, and the ascending list of non-empty keys with
 //                    their segment starts (order-preserving; tiles + one-workgroup tile scan)
 //   lw_key_scatter   values of the window's panes into their key segments as f64 order bits
+//
+// Distinct count (func "distinct"): segment_distinct_count = the number of different 64-bit
+// words of every gathered segment, exact (a hash set, not a sort and not a sketch). A segment of
+// up to kDistinctLds words is counted by one wave in an open-addressed LDS table of at most
+// 2 * kDistinctLds slots (segment_distinct_short, which also reserves 2n words of a device
+// scratch for every longer segment and lists it); the listed segments are then counted by many
+// workgroups with global compare-and-swap into their scratch tables (segment_distinct_long).
+// The all-ones word marks an empty slot and is never inserted: a wave / workgroup notes that it
+// saw one and the segment counts one more. Both probe loops are bounded by the table size; a
+// bound that is hit sets meta[kDistinctErr].
 #pragma once
 #include <cstdint>
 
@@ -33,6 +43,19 @@ struct LwPanes {
   LwPane p[kLwMaxPanes];
   int32_t n;
 };
+
+// segment_distinct_count: segments of up to kDistinctLds words are counted in LDS, longer ones
+// in a device scratch. meta (int64[kDistinctMeta], zeroed by the caller before the short pass):
+// [kDistinctCursor] = (number of long segments << kDistinctWordBits) | scratch words reserved
+// (one atomic reserves both, so list order = scratch order), [kDistinctErr] != 0 when a probe
+// bound was hit. The list of long segments holds kDistinctEntry words each: segment id, base
+// of its 2n-word table in the scratch, "the empty marker was seen" (zeroed by the caller).
+constexpr int kDistinctLds = 1024;
+constexpr uint64_t kDistinctEmpty = ~0ull;
+constexpr int kDistinctWordBits = 40;
+constexpr int kDistinctMeta = 2, kDistinctCursor = 0, kDistinctErr = 1;
+constexpr int kDistinctEntry = 3;
+constexpr int kDistinctTile = 4096;  // long-segment elements per workgroup step
 
 // Arena targets of a batch scatter: a table (device memory for the GPU launch) of 5 * ring
 // words -- [r] the key buffer of ring slot r, [ring + r] its value buffer, [2 ring + r] its
@@ -75,6 +98,17 @@ void lw_rank_prefix(const LwRankPanes& w, int64_t kmin, int64_t nkeys, uint32_t*
                     uint32_t* pre, intptr_t stream);
 void lw_rank_scatter(const LwRankPanes& w, int64_t kmin, int64_t nkeys, const int64_t* offs,
                      const uint32_t* pre, uint64_t* out_ord, intptr_t stream);
+// out[s] = distinct words of segment s for every segment of <= kDistinctLds words; a longer one
+// gets out[s] = 0, a table reserved in the scratch and an entry in `list` (list_cap entries; at
+// most total / (kDistinctLds + 1) can exist).
+void segment_distinct_short(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
+                            int64_t* out, int64_t* list, int64_t list_cap, int64_t* meta,
+                            intptr_t stream);
+// The n_long listed segments (long_elems words in all) counted into out[s]; `scratch` holds the
+// reserved tables, filled with kDistinctEmpty by the caller.
+void segment_distinct_long(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
+                           int64_t* list, int64_t n_long, int64_t long_elems, uint64_t* scratch,
+                           int64_t* out, int64_t* meta, intptr_t stream);
 }  // namespace gpu
 
 namespace cpu {
@@ -91,6 +125,9 @@ void lw_rank_prefix(const LwRankPanes& w, int64_t kmin, int64_t nkeys, uint32_t*
                     uint32_t* pre);
 void lw_rank_scatter(const LwRankPanes& w, int64_t kmin, int64_t nkeys, const int64_t* offs,
                      const uint32_t* pre, uint64_t* out_ord);
+// The oracle of the two kernels above by another method: sort a copy, count the boundaries.
+void segment_distinct_count(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
+                            int64_t* out);
 }  // namespace cpu
 
 // Java floorDiv for the pane of a timestamp.

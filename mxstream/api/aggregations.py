@@ -1,5 +1,5 @@
-"""Builtin AggregateFunctions (and one ProcessWindowFunction, WindowQuantiles) that the planner
-can run natively.
+"""Builtin AggregateFunctions (and two ProcessWindowFunctions, WindowQuantiles and
+WindowDistinctCount) that the planner can run natively.
 
 Each behaves exactly like the equivalent hand-written Flink AggregateFunction on the host path
 (e.g. ``AvgAggregate(1)`` is ComputeCpuAvg.java:31-58: accumulator (count, sum), result
@@ -250,3 +250,32 @@ class WindowTopN(ProcessWindowFunction):
     def process(self, key, context, elements, out):
         for e in self.rank(elements):
             out.collect(e)
+
+
+class WindowDistinctCount(ProcessWindowFunction):
+    """Per key and window, the number of different values of one field: ``process`` emits one
+    ``Tuple(key, count)``, the count a Python int (Java prints the Long: ``(host1,42)``). The
+    count is exact, never a sketch.
+
+    Equality is Java's ``equals`` of the boxed value: doubles by ``Double.equals`` (the order
+    bits of ``_double_order``: every NaN is one value, -0.0 and 0.0 are two), everything else by
+    Python equality, and an int never equals a float (a ``Long`` is no ``Double``).
+
+    ``native`` hands the field to the planner, which runs tumbling and sliding event-time
+    windows on the device list-window operator (a hash set per key over the pane arena; float
+    fields, and int fields up to 2**53 in magnitude); this method is the exact host
+    implementation used otherwise."""
+
+    def __init__(self, field: int):
+        if isinstance(field, bool) or not isinstance(field, int) or field < 0:
+            raise ValueError(f"WindowDistinctCount takes a field index >= 0, got {field!r}")
+        self.field = field
+        self.native = ("distinct", field)
+
+    def process(self, key, context, elements, out):
+        seen = set()
+        for t in elements:
+            v = t[self.field]
+            # the tag keeps 1 and 1.0 (equal in Python) apart
+            seen.add(("double", _double_order(v)) if isinstance(v, float) else ("object", v))
+        out.collect(Tuple([key, len(seen)]))

@@ -6,7 +6,8 @@ runs:
   * assigner: tumbling/sliding, event or processing time, default trigger, no evictor;
   * key: keyBy(<int field>);
   * function: ``sum/min/max(pos)``, a builtin aggregate (api/aggregations.py), a ``process``
-    function with a ``native`` descriptor (the median, ``WindowQuantiles``), or a reduce
+    function with a ``native`` descriptor (the median, ``WindowQuantiles``,
+    ``WindowDistinctCount``), or a reduce
     lambda whose trace is "field pos = a.pos + b.pos, every other field = a's" (Flink's
     ``reduce((a, b) -> new TupleN(a.f0, .., a.fk + b.fk, ..))``, BandwidthMonitor.java:37);
   * keep-first fields other than the key are dead: the only consumer is a map whose traced
@@ -326,6 +327,13 @@ def plan(env, sinks):
             kind, val_pos = "quantiles", spec.fn.native[1]
             result = "tuple"  # NativeMedianOp builds the (key, x_1..x_Q) rows itself
             ok_arities = set(range(max(key_pos, val_pos) + 1, 64))
+        elif spec.kind == "process" and getattr(spec.fn, "native", (None,))[0] == "distinct" \
+                and not session and a.is_event_time():
+            # WindowDistinctCount(field), the same windows as the quantiles: (key, count) rows
+            # from a hash set over the median's pane arena; anything else: host operator
+            kind, val_pos = "distinct", spec.fn.native[1]
+            result = "tuple"  # NativeMedianOp builds the (key, count) rows itself
+            ok_arities = set(range(max(key_pos, val_pos) + 1, 64))
         elif spec.kind == "reduce" and spec.window_fn is None:
             result = "tuple"
             for ar in range(2, 9):
@@ -627,7 +635,7 @@ def _install_native(env, t, ws, spec, key_pos, val_pos, kind, result, ok_arities
     if session and kind in ("vsum", "vavg"):
         return  # merging windows over vectors: exact host operator
     cls = NativeSessionOp if session else (
-        NativeMedianOp if kind in ("median", "quantiles") else
+        NativeMedianOp if kind in ("median", "quantiles", "distinct") else
         NativeVectorWindowOp if kind in ("vsum", "vavg") else NativeWindowOp)
     # Input straight from the device ingest: the operator knows its column kinds up front and
     # shares the ingest's dictionary (the G > 1 device exchange needs both before any data).

@@ -657,19 +657,25 @@ def config6(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_000
 
 
 def config8(steps: int, warmup: int, batch: int = 1 << 22, keys: int = 100_000,
-            device: str = "cuda", quantiles=None) -> dict:
+            device: str = "cuda", quantiles=None, distinct: bool = False) -> dict:
     """Process-window median at scale (ComputeCpuMiddle.java:34-48 shape): per host, the median
     CPU usage of every 1-min tumbling event-time window over `keys` hosts; every element is kept
     (ListState analogue, runtime/list_window_operator.py) and each firing sorts the window's
     values by host (one radix sort over the host-id bits) and selects each host's median
     (segment_median_select: LDS bitonic sort / radix select per segment).
     quantiles (e.g. [0.5, 0.95, 0.99]): the same window with WindowQuantiles' function instead
-    of the median -- Q nearest-rank quantiles per host from one firing."""
+    of the median -- Q nearest-rank quantiles per host from one firing.
+    distinct: the same window with WindowDistinctCount's function -- per host, the number of
+    different values (the generator draws them from 10,000 possibilities) from one firing."""
     from ..runtime.list_window_operator import KeyedListWindowOperator
 
     dev = torch.device(device)
     step_ms, disorder = 5_000, 1_000
-    if quantiles:
+    if quantiles and distinct:
+        raise ValueError("config 8: --quantiles and --distinct exclude each other")
+    if distinct:
+        op = KeyedListWindowOperator(size=60_000, device=dev, func="distinct")
+    elif quantiles:
         from ..api.aggregations import WindowQuantiles
 
         ppm = WindowQuantiles(1, quantiles).ppm
@@ -716,6 +722,8 @@ def config8(steps: int, warmup: int, batch: int = 1 << 22, keys: int = 100_000,
     if quantiles:
         res["metric"] = f"events/sec (process-window {len(ppm)} quantiles per key, ListState)"
         res["quantiles_ppm"] = list(ppm)
+    if distinct:
+        res["metric"] = "events/sec (process-window distinct count per key, ListState)"
     return res
 
 
@@ -1036,6 +1044,8 @@ def main(argv=None) -> int:
     ap.add_argument("--quantiles", default=None,
                     help="config 8: comma-separated quantiles in [0, 1] (e.g. 0.5,0.95,0.99) "
                          "instead of the median")
+    ap.add_argument("--distinct", action="store_true",
+                    help="config 8: the exact per-key distinct count instead of the median")
     ap.add_argument("--threads", type=int, default=4,
                     help="config 1 CPU path: parse threads (the reference job runs at P = 4)")
     a = ap.parse_args(argv)
@@ -1063,7 +1073,8 @@ def main(argv=None) -> int:
                     batch_lines=a.batch or (1 << 20))
     elif a.config == 8:
         r = config8(a.steps, a.warmup, a.batch or (1 << 22), device=a.device,
-                    quantiles=[float(x) for x in a.quantiles.split(",")] if a.quantiles else None)
+                    quantiles=[float(x) for x in a.quantiles.split(",")] if a.quantiles else None,
+                    distinct=a.distinct)
     elif a.config == 10:
         r = config10(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 1_000_000,
                      device=a.device, top_n=a.top_n)

@@ -619,3 +619,65 @@ def topn_select(keys: torch.Tensor, vals: torch.Tensor, raw: torch.Tensor | None
     else:
         m.cpu_topn_select(cols, _p(bounds), plan, out, _p(obounds))
     return okeys, ovals, oraw, ocnt, obounds
+
+
+def segment_distinct_launch(heads: torch.Tensor, nseg: int, total: int, ord_bits: torch.Tensor):
+    """Launch the distinct count of the `nseg` segments of `ord_bits[:total]` (operands already
+    validated). Returns (int64 [nseg] counts, meta): `meta` is the device error word holder to
+    pass to ``segment_distinct_check`` after the caller's next readback (None on the CPU).
+
+    GPU: segments of up to 1024 words are counted in LDS by one pass; longer ones are listed by
+    it, and only when `total` allows one to exist are (n_long, scratch words) read back (one
+    small D2H), the scratch (2 words per element of the long segments, never 2 * total)
+    allocated and filled with the empty marker, and the second pass launched."""
+    dev = ord_bits.device
+    out = torch.empty(nseg, dtype=torch.int64, device=dev)
+    if not nseg:
+        return out, None
+    m = load()
+    if not _is_gpu(ord_bits):
+        m.cpu_segment_distinct_count(heads.data_ptr(), nseg, total, ord_bits.data_ptr(),
+                                     out.data_ptr())
+        return out, None
+    st = _stream(ord_bits)
+    list_cap = max(1, total // (m.DISTINCT_LDS + 1))
+    buf = torch.zeros(m.DISTINCT_META + list_cap * m.DISTINCT_ENTRY, dtype=torch.int64, device=dev)
+    meta, lst = buf[:m.DISTINCT_META], buf[m.DISTINCT_META:]
+    m.gpu_segment_distinct_short(heads.data_ptr(), nseg, total, ord_bits.data_ptr(), out.data_ptr(),
+                                 lst.data_ptr(), list_cap, meta.data_ptr(), st)
+    if total > m.DISTINCT_LDS:
+        cursor, err = meta.tolist()
+        n_long, words = cursor >> m.DISTINCT_WORD_BITS, cursor & ((1 << m.DISTINCT_WORD_BITS) - 1)
+        if err or n_long > list_cap or words > 2 * total:
+            raise RuntimeError(f"segment_distinct: long-segment list overflow ({n_long} segments, "
+                               f"{words} words, error word {err})")
+        if n_long:
+            scratch = torch.full((words,), -1, dtype=torch.int64, device=dev)  # the empty marker
+            m.gpu_segment_distinct_long(heads.data_ptr(), nseg, total, ord_bits.data_ptr(),
+                                        lst.data_ptr(), n_long, words // 2, scratch.data_ptr(),
+                                        out.data_ptr(), meta.data_ptr(), st)
+    return out, meta
+
+
+def segment_distinct_check(meta) -> None:
+    """Raise if a probe loop of the distinct kernels hit its bound (tables are at most half
+    full, so it never should): the counts of that launch are not to be trusted."""
+    if meta is not None:
+        err = int(meta[load().DISTINCT_ERR])
+        if err:
+            raise RuntimeError(f"segment_distinct: probe bound hit (error word {err})")
+
+
+def segment_distinct(heads: torch.Tensor, ord_bits: torch.Tensor) -> torch.Tensor:
+    """Number of different 64-bit words in every segment of `ord_bits` starting at `heads`
+    (words in any order, any 64-bit pattern): int64 [nseg], exact; 0 for an empty segment."""
+    dev = ord_bits.device
+    _check(heads, torch.int64, heads.numel(), "heads", dev)
+    _check(ord_bits, torch.int64, ord_bits.numel(), "ord", dev)
+    if heads.numel() and (int(heads[0]) != 0 or int(heads[-1]) >= max(1, ord_bits.numel())):
+        raise ValueError("segment heads out of range")
+    if heads.numel() > 1 and bool((heads[1:] < heads[:-1]).any()):
+        raise ValueError("segment heads must ascend")
+    out, meta = segment_distinct_launch(heads, heads.numel(), ord_bits.numel(), ord_bits)
+    segment_distinct_check(meta)
+    return out

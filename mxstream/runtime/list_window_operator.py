@@ -15,7 +15,10 @@ a power-of-two ring of pane slots, each an append buffer of (key, f64 bits) on t
   placed at segment start + prefix + rank (``lw_rank_scatter``, as order bits), and each
   segment's median selected in LDS (``segment_median_select``) -- or, for
   ``func=("quantiles", ppm)``, up to 8 nearest-rank quantiles from one staged copy of the
-  segment (``segment_quantile_select``). Panes without ranks (wide key
+  segment (``segment_quantile_select``) -- or, for ``func="distinct"``, the number of
+  different values of the segment counted exactly in a hash set (``segment_distinct_short`` /
+  ``segment_distinct_long``; equality of the order bits = Java's ``Double.equals``: every NaN
+  is one value, -0.0 and 0.0 are two). Panes without ranks (wide key
   ranges, restored panes) fire through a counting sort with atomics (``lw_key_count`` /
   ``lw_key_scatter``); key ranges over 16 Mi ids are mapped to dense ids first. No comparison
   sort of the window, no per-pane host loop.
@@ -49,13 +52,17 @@ class KeyedListWindowOperator:
                  lateness: int = 0, device="cpu", time_mode: str = "event", func="median"):
         slide = size if slide is None else slide
         # func: "median" (fired res = one f64 per key) or ("quantiles", (ppm, ...)) -- 1..8
-        # nearest-rank quantiles in parts per million (fired res = [Q, k] f64, row j = ppm[j]).
-        if func == "median":
+        # nearest-rank quantiles in parts per million (fired res = [Q, k] f64, row j = ppm[j]),
+        # or "distinct" (fired res = one int64 per key: its number of different values).
+        self.distinct = func == "distinct"
+        self._distinct_meta = None  # device error word of the last distinct launch
+        if func == "median" or self.distinct:
             self.ppm = None
         elif isinstance(func, (tuple, list)) and len(func) == 2 and func[0] == "quantiles":
             self.ppm = list(K.check_ppm(func[1]))
         else:
-            raise ValueError('supported list-window functions: "median", ("quantiles", (ppm, ...))')
+            raise ValueError('supported list-window functions: "median", "distinct", '
+                             '("quantiles", (ppm, ...))')
         self.size, self.slide, self.offset, self.lateness = int(size), int(slide), int(offset), int(lateness)
         self.pane = math.gcd(self.size, self.slide)
         self.ppw = self.size // self.pane
@@ -193,7 +200,7 @@ class KeyedListWindowOperator:
     def process(self, keys: torch.Tensor, ts: torch.Tensor, vals_f64: torch.Tensor) -> list:
         """keys int64 (or int32 dictionary ids), ts int64, vals: f64 bit patterns (int64).
         Returns fired rows (window_start, window_end, keys, res) of late re-firings; res is
-        the medians [k], or the quantiles [Q, k]."""
+        the medians [k], the quantiles [Q, k], or the distinct counts [k] (int64)."""
         n = keys.numel()
         if n == 0:
             return []
@@ -334,12 +341,19 @@ class KeyedListWindowOperator:
         if not keys_out.numel():
             return []
         self.metrics.num_records_out += int(keys_out.numel())
-        return [(s, s + self.size, keys_out.cpu().numpy(), med.cpu().numpy())]
+        row = (s, s + self.size, keys_out.cpu().numpy(), med.cpu().numpy())
+        if self.distinct:  # the kernels' error word, read after the readback above drained the stream
+            K.segment_distinct_check(self._distinct_meta)
+        return [row]
 
     def _select(self, heads: torch.Tensor, k: int, total: int, ordv: torch.Tensor) -> torch.Tensor:
         """The window function over the k key segments of order bits in `ordv`: the medians
-        [k], or the nearest-rank quantiles [Q, k] (one column per quantile, one kernel)."""
+        [k], the nearest-rank quantiles [Q, k] (one column per quantile, one kernel), or the
+        distinct counts int64 [k]."""
         m = self._m
+        if self.distinct:
+            res, self._distinct_meta = K.segment_distinct_launch(heads, k, total, ordv)
+            return res
         shape = (k,) if self.ppm is None else (len(self.ppm), k)
         res = torch.empty(shape, dtype=torch.float64, device=self.device)
         if not k:

@@ -267,6 +267,15 @@ class NativeWindowOp(_ColumnInput, Operator):
             self._build(1.0 if self.is_float else 1, dense=True)
         self.op.restore_state(es.columns, es.meta)
 
+    def _value_bits(self, col):
+        """A numeric value column (numpy or torch; float64 or integers) as the int64 words the
+        engine stores: a double's bit pattern, an integer as it is. Every ingest path ends
+        here; an operator that stores something else overrides it (NativeMedianOp: integers of
+        a distinct count) and raises TypeError for a column it cannot carry."""
+        if isinstance(col, np.ndarray):
+            return np.ascontiguousarray(col).view(np.int64)
+        return col.view(torch.int64) if col.dtype == torch.float64 else col.to(torch.int64)
+
     def _local_columns(self, data: list):
         """This rank's (key id, timestamp, value bits) device columns of a pass (empty columns
         when it got no rows). Processing time: every row carries the step's agreed time."""
@@ -283,8 +292,7 @@ class NativeWindowOp(_ColumnInput, Operator):
                                                                      dtype=torch.int64, device=dev)
             else:
                 ts = torch.full((n,), self.ctx.clock(), dtype=torch.int64, device=dev)
-            vals = cb.cols[self.val_pos][:n]
-            vals = vals.view(torch.int64) if vals.dtype == torch.float64 else vals.to(torch.int64)
+            vals = self._value_bits(cb.cols[self.val_pos][:n])
         else:
             kid = torch.empty(0, dtype=torch.int32 if self.str_keys else torch.int64, device=dev)
             ts = torch.empty(0, dtype=torch.int64, device=dev)
@@ -407,6 +415,7 @@ class NativeWindowOp(_ColumnInput, Operator):
                     raise TypeError("unsupported value")
             elif (vk == FK_DOUBLE) != self.is_float:
                 raise TypeError("mixed value types")
+            vals = self._value_bits(cb.cols[self.val_pos][:cb.n])
         except TypeError:
             if self.templates or getattr(self, "_lazy_tpl", None):
                 raise
@@ -423,8 +432,6 @@ class NativeWindowOp(_ColumnInput, Operator):
                                                                  device=dev)
         else:
             ts = torch.full((n,), self.ctx.clock(), dtype=torch.int64, device=dev)
-        vals = cb.cols[self.val_pos][:n]
-        vals = vals.view(torch.int64) if vals.dtype == torch.float64 else vals.to(torch.int64)
         if kid.dtype == torch.int32 and not self._key32_ok:
             kid = kid.to(torch.int64)
         late_before = self.op.metrics.num_late_records_dropped
@@ -459,6 +466,8 @@ class NativeWindowOp(_ColumnInput, Operator):
             elif (vk == FK_DOUBLE) != self.is_float:
                 raise TypeError("mixed value types")
             kid = self._cb_keys(cb)
+            vbits = self._value_bits(cb.cols[self.val_pos].astype(
+                np.float64 if self.is_float else np.int64, copy=False))
         except TypeError:
             if self.templates:
                 raise
@@ -472,12 +481,11 @@ class NativeWindowOp(_ColumnInput, Operator):
             tsa = cb.ts if cb.ts is not None else np.full(cb.n, LONG_MIN, dtype=np.int64)
         else:
             tsa = np.full(cb.n, self.ctx.clock(), dtype=np.int64)
-        vv = cb.cols[self.val_pos].astype(np.float64 if self.is_float else np.int64, copy=False)
         dev = self.op.device
         late_before = self.op.metrics.num_late_records_dropped
         fired = self.op.process(torch.from_numpy(np.ascontiguousarray(kid)).to(dev),
                                 torch.from_numpy(np.ascontiguousarray(tsa, dtype=np.int64)).to(dev),
-                                torch.from_numpy(np.ascontiguousarray(vv).view(np.int64)).to(dev))
+                                torch.from_numpy(vbits).to(dev))
         if getattr(self.op, "late_side", None):
             for idx in np.concatenate(self.op.late_side).tolist():
                 sub = int(cb.sub[idx]) if cb.sub is not None else 0
@@ -522,6 +530,7 @@ class NativeWindowOp(_ColumnInput, Operator):
                 if isinstance(x, float) != self.is_float:
                     raise TypeError("mixed value types")
                 vv[i] = x
+            vbits = self._value_bits(vv)
         except TypeError:
             # Unsupported data for the native path: switch to the exact host operator.
             self._to_fallback()
@@ -529,7 +538,7 @@ class NativeWindowOp(_ColumnInput, Operator):
         dev = self.op.device
         kt = torch.from_numpy(kid).to(dev)
         tt = torch.from_numpy(tsa).to(dev)
-        vt = torch.from_numpy(vv.view(np.int64)).to(dev)
+        vt = torch.from_numpy(vbits).to(dev)
         late_before = self.op.metrics.num_late_records_dropped
         fired = self.op.process(kt, tt, vt)
         if self.op.late_side:
@@ -1332,23 +1341,47 @@ class NativeMedianOp(NativeWindowOp):
     counting-sorts the window by key id and a kernel selects each key's median.
     ``process(WindowQuantiles(field, qs))`` (kind "quantiles") runs on the same arena: the
     kernel selects the Q nearest-rank quantiles of each key and the rows are (key, x_1..x_Q).
+    ``process(WindowDistinctCount(field))`` (kind "distinct") counts each key's different
+    values in a hash set on the device and the rows are (key, count). Its field may also hold
+    integers: they are carried in the arena as the bit pattern of ``float(x)``, exact and
+    injective for |x| <= 2**53 (ids, addresses, ports); a larger one is "mixed value types".
     Checkpoints carry the live panes' elements (NativeWindowOp.snapshot -> snapshot_state)."""
 
     _key32_ok = False
     quantiles_ppm = None  # planner: the quantiles (parts per million) of kind "quantiles"
+    _INT_EXACT = 1 << 53  # every integer up to here is a double
+
+    def _value_bits(self, col):
+        """Integers of a distinct count as the bit patterns of ``float(x)``; a column with one
+        beyond 2**53 raises TypeError (the flush paths catch it: host operator; the G > 1 device
+        exchange has no host route and the job ends with it)."""
+        if self.kind != "distinct" or self.is_float:
+            return super()._value_bits(col)
+        host = isinstance(col, np.ndarray)
+        col = col.astype(np.int64, copy=False) if host else col.to(torch.int64)
+        if (col.size if host else col.numel()):
+            lo, hi = (int(col.min()), int(col.max())) if host else \
+                torch.stack([col.min(), col.max()]).tolist()
+            if lo < -self._INT_EXACT or hi > self._INT_EXACT:
+                raise TypeError("mixed value types")  # not every value is a double: host operator
+        if host:
+            return col.astype(np.float64).view(np.int64)
+        return col.to(torch.float64).view(torch.int64)
 
     def _build(self, sample_val, dense: bool = False) -> bool:
         from .list_window_operator import KeyedListWindowOperator
 
-        if not isinstance(sample_val, float):
+        is_int = isinstance(sample_val, int) and not isinstance(sample_val, bool)
+        if not isinstance(sample_val, float) and not (self.kind == "distinct" and is_int):
             return False  # the reference's values are Double; anything else: host operator
-        self.is_float = True
+        self.is_float = isinstance(sample_val, float)
         a = self.assigner
         self.op = KeyedListWindowOperator(
             size=a.size, slide=a.slide, offset=a.offset,
             lateness=self.lateness if a.is_event_time() else 0, device=torch.device(self.device),
             time_mode="event" if a.is_event_time() else "processing",
-            func=("quantiles", self.quantiles_ppm) if self.kind == "quantiles" else "median")
+            func=("quantiles", self.quantiles_ppm) if self.kind == "quantiles" else
+            ("distinct" if self.kind == "distinct" else "median"))
         comm = getattr(self, "comm", None)
         if comm is not None and comm.world > 1:
             # G > 1: the pane arena holds this rank's key groups; records reach their owner by
@@ -1389,6 +1422,8 @@ class NativeMedianOp(NativeWindowOp):
             return []
         if self.kind == "quantiles":
             return self._emit_quantiles(fired)
+        if self.kind == "distinct":
+            return self._emit_distinct(fired)
         if self.scalar_result:
             keys = np.concatenate([np.asarray(f[2]) for f in fired]).astype(np.int64)
             med = np.concatenate([np.asarray(f[3]) for f in fired]).astype(np.float64)
@@ -1419,6 +1454,16 @@ class NativeMedianOp(NativeWindowOp):
         kinds = (FK_STR if self.str_keys else FK_LONG,) + (FK_DOUBLE,) * qs.shape[0]
         return [ColumnBatch(int(keys.size), cols, kinds, self.dict if self.str_keys else None, ts,
                             self._subtasks(keys), False)]
+
+    def _emit_distinct(self, fired) -> list:
+        """(key, count) rows of all fired windows as one ColumnBatch of (key kind, FK_LONG)."""
+        keys = np.concatenate([np.asarray(f[2]) for f in fired]).astype(np.int64)
+        cnt = np.concatenate([np.asarray(f[3], dtype=np.int64) for f in fired])
+        ts = np.repeat(np.array([f[1] - 1 for f in fired], dtype=np.int64),
+                       [len(f[2]) for f in fired])
+        kinds = (FK_STR if self.str_keys else FK_LONG, FK_LONG)
+        return [ColumnBatch(int(keys.size), [keys, cnt], kinds,
+                            self.dict if self.str_keys else None, ts, self._subtasks(keys), False)]
 
 
 class NativeVectorWindowOp(NativeWindowOp):
