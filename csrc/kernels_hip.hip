@@ -1068,6 +1068,326 @@ __global__ __launch_bounds__(1024) void partition_compact_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// One-pass compact partition: 8-byte RecN records, one destination, <= 512 buckets.
+// The two-pass kernel above reads the key column twice (a histogram pass, so that a workgroup's
+// records of a bucket form one run) and sorts 4096-record rounds. Here a round of 1024 * RU
+// records is held in registers (record: two words, bucket | rank: one word), ranked with LDS
+// atomics while it streams in, and the run of every bucket is reserved once per round: no
+// histogram pass, three barriers per round, and run pieces of R / nb records.
+// Per round: load + rank (sub-steps of kOpSub events per thread, the next sub-step's loads in
+// flight) | barrier | wave 0 scans the counts | barrier | reserve (one returning atomic per
+// bucket, not waited for), place into the LDS round buffer sorted by bucket, publish the
+// bases | barrier | flush by bucket: wave w writes buckets w, w + 16, ... as 16-byte stores of
+// whole 32-byte granules, holes included.
+// Dropped events (late, invalid) are not counted and cost no hole. A round in which a
+// reservation passes bucket_cap sets the overflow bit and writes nothing, nor does any later
+// round of the group (the host redoes the step).
+// ------------------------------------------------------------------------------------------
+constexpr int kOpSub = 4;  // events per thread and sub-step
+// Inclusive wave64 prefix sum by DPP row shifts and row broadcasts: no LDS round trip and no
+// per-lane index registers (the shuffle form keeps six of them live across the whole kernel).
+__device__ __forceinline__ uint32_t wave_inclusive_scan_dpp(uint32_t x) {
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);  // row_shr:1
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);  // row_shr:2
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);  // row_shr:4
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);  // row_shr:8
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);  // row_bcast:15
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);  // row_bcast:31
+  return x;
+}
+constexpr size_t onepass_lds(int ru) {
+  return (size_t)1024 * ru * 8 + (size_t)(3 * kCMaxNb + 4) * 4 + 20 * 4 + 16 * 8;
+}
+static_assert(kCG == kPartGranule, "reservation granule differs from the host's capacity bound");
+static_assert(onepass_lds(kOnePassRound / 1024) <= 160 * 1024, "one-pass round exceeds 160 KiB");
+
+template <int V, int RU, bool K32, bool PAIR>
+__global__ __launch_bounds__(1024) void partition_onepass_kernel(
+    const uint64_t* __restrict__ keys, const int64_t* __restrict__ ts,
+    const uint64_t* __restrict__ vals, int64_t n, int64_t chunk, PartPlan plan,
+    uint32_t* __restrict__ cursor, uint2* __restrict__ out, int64_t* __restrict__ stats,
+    uint32_t* __restrict__ late_idx, uint32_t late_cap) {
+  static_assert(RU % kOpSub == 0, "a round is a whole number of sub-steps");
+  constexpr int R = 1024 * RU, NS = RU / kOpSub, SUB = 1024 * kOpSub;
+  constexpr uint32_t kDropped = 0xFFFFFFFFu;
+  extern __shared__ __attribute__((aligned(16))) unsigned char osm[];
+  const int nb = 1 << plan.nsub_log2;
+  uint2* rbuf = (uint2*)osm;                  // [R] the round, sorted by bucket
+  uint32_t* rcnt = (uint32_t*)(rbuf + R);     // [kCMaxNb] this round's count per bucket
+  uint32_t* roff = rcnt + kCMaxNb;            // [kCMaxNb + 1] this round's offsets (+ total)
+  uint32_t* gbase = roff + kCMaxNb + 4;       // [kCMaxNb] record index of the reserved run
+  uint32_t* wsum = gbase + kCMaxNb;           // [17] accepted, [18] overflow, [19] max fill
+  int64_t* lred = (int64_t*)(wsum + 20);      // 16 x i64
+
+  for (int b = threadIdx.x; b < kCMaxNb; b += blockDim.x) rcnt[b] = 0;
+  if (threadIdx.x == 0) {
+    wsum[17] = 0;
+    wsum[18] = 0;
+    wsum[19] = 0;
+  }
+  __syncthreads();
+  const int64_t start = (int64_t)blockIdx.x * chunk;
+  const int64_t end = start + chunk < n ? start + chunk : n;
+  const uint32_t bcap = plan.bucket_cap;
+
+  // The thread index behind an opaque copy: everything derived from it (column offsets, LDS
+  // addresses of the scan, reserve and flush steps) is recomputed where it is used -- hoisted
+  // out of the round loop, those values alone took nine registers more than there are.
+  auto tid_now = [&]() -> uint32_t {
+    uint32_t t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+  };
+  // Event u of a thread's sub-step, as a 32-bit offset from the sub-step's (uniform) first
+  // event: lane-strided, or (PAIR) two consecutive events per lane.
+  auto ev_off = [&](int u) -> uint32_t {
+    if constexpr (PAIR) return (uint32_t)(u >> 1) * 2048u + 2u * tid_now() + (uint32_t)(u & 1);
+    else return (uint32_t)u * 1024u + tid_now();
+  };
+  // Events of the sub-step at `base` that lie inside this group's chunk (0 .. SUB).
+  auto sub_len = [&](int64_t base) -> uint32_t {
+    const int64_t rem = end - base;
+    return rem <= 0 ? 0u : rem >= SUB ? (uint32_t)SUB : (uint32_t)rem;
+  };
+  uint64_t nk[kOpSub], nv[kOpSub];
+  int64_t nt[kOpSub];
+  // Loads events 2h and 2h + 1 of the sub-step at `base` (h < kOpSub / 2).
+  auto load_half = [&](int64_t base, int h) {
+    const uint32_t len = sub_len(base);
+    const uint64_t* kb = K32 ? reinterpret_cast<const uint64_t*>(
+                                   reinterpret_cast<const int32_t*>(keys) + base)
+                             : keys + base;
+    const int64_t* tb = ts + base;
+    const uint64_t* vb = vals + base;
+    if constexpr (PAIR) {
+      {
+        const int u = 2 * h;
+        const uint32_t o = ev_off(u);
+        if (o + 1 < len) {
+          ldkey2<V, K32>(kb, o, nk[u], nk[u + 1]);
+          uint64_t t0, t1;
+          ld64x2<V>(tb, o, t0, t1);
+          nt[u] = (int64_t)t0;
+          nt[u + 1] = (int64_t)t1;
+          ld64x2<V>(vb, o, nv[u], nv[u + 1]);
+        } else if (o < len) {
+          nk[u] = ldkey<V, K32>(kb, o);
+          nt[u] = ldin<V>(&tb[o]);
+          nv[u] = ldin<V>(&vb[o]);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 2 * h; u < 2 * h + 2; ++u) {
+        const uint32_t o = ev_off(u);
+        if (o < len) {
+          nk[u] = ldkey<V, K32>(kb, o);
+          nt[u] = ldin<V>(&tb[o]);
+          nv[u] = ldin<V>(&vb[o]);
+        }
+      }
+    }
+  };
+  static_assert(kOpSub == 4, "a sub-step is two halves of two events");
+
+  // Per-thread statistics; the accepted count and the largest fill are kept in LDS
+  // (wsum[17], wsum[19]) to spare registers.
+  int64_t tmax = INT64_MIN;
+  uint32_t nlate = 0, qmin32 = 0xFFFFFFFFu, qmax32 = 0, pmask = 0, flags = 0;
+  const bool pane32 = plan.window_mode && plan.pane > 0 && plan.pane < ((int64_t)1 << 31);
+  const uint32_t pane_u = (uint32_t)plan.pane;
+  load_half(start, 0);
+  load_half(start, 1);
+  for (int64_t r0 = start; r0 < end; r0 += R) {
+    uint2 rec[RU];
+    uint32_t br[RU];  // bucket << 16 | rank in the round's bucket; kDropped: no record
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const int64_t s0 = r0 + (int64_t)s * SUB;
+      const uint32_t len = sub_len(s0);
+      // The two-pass kernel's wave-vote fast path and general per-lane path, per sub-step.
+      // The column registers are single-buffered (a second set does not fit under 128 VGPRs
+      // next to the round's records): each half of the next sub-step is loaded as soon as
+      // this sub-step's half has been evaluated.
+      bool simple = len == (uint32_t)SUB && pane32 && !(plan.ablate & 8u);
+      if (simple) {
+        // (An opaque copy of tbase: the differences must die with the vote. Shared with the
+        // evaluation below, four 64-bit values per sub-step stay live and spill.)
+        int64_t tbase_v = plan.tbase;
+        asm volatile("" : "+s"(tbase_v));
+        bool ok = true;
+#pragma unroll
+        for (int u = 0; u < kOpSub; ++u) {
+          const int64_t d = nt[u] - tbase_v;
+          ok = ok && nk[u] < kTombKey && !(plan.drop_late && nt[u] < plan.late_ts) && d >= 0 &&
+               d < ((int64_t)1 << 31);
+        }
+        simple = __all(ok);
+      }
+      if (simple) {
+#pragma unroll
+        for (int u = 0; u < kOpSub; ++u) {
+          const uint64_t k = nk[u];
+          const int64_t t = nt[u];
+          const uint64_t v = nv[u];
+          tmax = t > tmax ? t : tmax;
+          const uint32_t du = (uint32_t)(t - plan.tbase);
+          uint32_t q = (uint32_t)((double)du * plan.inv_pane);
+          const uint32_t qp = q * pane_u;
+          q = qp > du ? q - 1u : (du - qp >= pane_u ? q + 1u : q);
+          qmin32 = q < qmin32 ? q : qmin32;
+          pmask |= pane_bit(q);
+          qmax32 = q > qmax32 ? q : qmax32;
+          flags |= (int64_t)(int32_t)v != (int64_t)v ? 4u : 0u;  // needs 24-byte records
+          flags |= narrow_fits(k, (int64_t)v, q) ? 0u : 16u;      // needs 16-byte records
+          const uint32_t b = sub_of(k, plan);
+          rec[s * kOpSub + u] = make_uint2((uint32_t)k, ((uint32_t)v << 4) | (q & 15u));
+          br[s * kOpSub + u] = (b << 16) | atomicAdd(&rcnt[b], 1u);
+          if (u & 1) load_half(s0 + SUB, u >> 1);
+          // One event at a time: the scheduler otherwise interleaves the whole unrolled round
+          // and spills (the round's records already take most of the 128 VGPRs).
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
+        // General path (a late, reserved, out-of-range or missing event in the wave): one event
+        // at a time, not unrolled -- the selects keep the record registers' indices constant.
+#pragma unroll 1
+        for (int u = 0; u < kOpSub; ++u) {
+          uint64_t k = nk[0], v = nv[0];
+          int64_t t = nt[0];
+#pragma unroll
+          for (int j = 1; j < kOpSub; ++j)
+            if (u == j) {
+              k = nk[j];
+              t = nt[j];
+              v = nv[j];
+            }
+          uint32_t rx = 0, ry = 0, rb = kDropped;
+          const uint32_t o = ev_off(u);
+          if (o < len) {
+            tmax = t > tmax ? t : tmax;
+            const PartEval e = part_eval<true>(k, t, nullptr, plan, nullptr);
+            if (e.kind == 1) {
+              ++nlate;
+              if (late_idx) {
+                const unsigned long long pos =
+                    atomicAdd((unsigned long long*)&stats[kStatLate], 1ull);
+                if (pos < late_cap) late_idx[pos] = (uint32_t)(s0 + o);
+              }
+            } else if (e.kind >= 2) {
+              flags |= e.kind == 2 ? 2u : 8u;
+            } else {
+              if ((int64_t)(int32_t)v != (int64_t)v) flags |= 4u;  // needs 24-byte records
+              qmin32 = e.t < qmin32 ? e.t : qmin32;
+              pmask |= pane_bit(e.t);
+              qmax32 = e.t > qmax32 ? e.t : qmax32;
+              if (!narrow_fits(k, (int64_t)v, e.t)) flags |= 16u;  // needs 16-byte records
+              rx = (uint32_t)k;
+              ry = ((uint32_t)v << 4) | (e.t & 15u);
+              rb = (e.bucket << 16) | atomicAdd(&rcnt[e.bucket], 1u);
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < kOpSub; ++j)
+            if (u == j) {
+              rec[s * kOpSub + j] = make_uint2(rx, ry);
+              br[s * kOpSub + j] = rb;
+            }
+        }
+        load_half(s0 + SUB, 0);
+        load_half(s0 + SUB, 1);
+      }
+    }
+    __syncthreads();
+    const uint32_t tid = tid_now();
+    // Scan: wave 0 alone turns the counts into offsets, 8 buckets per lane (buckets >= nb
+    // count zero), and clears them for the next round; roff[nb ..] hold the round's total.
+    if (tid < 64) {
+      const uint4 c0 = ((const uint4*)rcnt)[2 * tid];
+      const uint4 c1 = ((const uint4*)rcnt)[2 * tid + 1];
+      ((uint4*)rcnt)[2 * tid] = make_uint4(0, 0, 0, 0);
+      ((uint4*)rcnt)[2 * tid + 1] = make_uint4(0, 0, 0, 0);
+      const uint32_t sum = c0.x + c0.y + c0.z + c0.w + c1.x + c1.y + c1.z + c1.w;
+      const uint32_t incl = wave_inclusive_scan_dpp(sum);
+      uint4 o0, o1;
+      o0.x = incl - sum;
+      o0.y = o0.x + c0.x;
+      o0.z = o0.y + c0.y;
+      o0.w = o0.z + c0.z;
+      o1.x = o0.w + c0.w;
+      o1.y = o1.x + c1.x;
+      o1.z = o1.y + c1.y;
+      o1.w = o1.z + c1.z;
+      ((uint4*)roff)[2 * tid] = o0;
+      ((uint4*)roff)[2 * tid + 1] = o1;
+      if (tid == 63) {
+        roff[kCMaxNb] = incl;
+        wsum[17] += incl;  // accepted events of the group
+      }
+    }
+    __syncthreads();
+    // Reserve: one returning atomic per bucket. The base is first used after the place step,
+    // so its round trip overlaps the LDS stores.
+    uint32_t c4 = 0, gb = 0;
+    if (tid < (unsigned)nb) {
+      c4 = (roff[tid + 1] - roff[tid] + (kCG - 1)) & ~(uint32_t)(kCG - 1);
+      if (c4) gb = atomicAdd(&cursor[tid], c4);
+    }
+#pragma unroll
+    for (int u = 0; u < RU; ++u)
+      if (br[u] != kDropped) rbuf[roff[br[u] >> 16] + (br[u] & 0xFFFFu)] = rec[u];
+    if (tid < (unsigned)nb) {
+      if (c4) {
+        // 64-bit: a cursor far past bucket_cap must not wrap back into range
+        if ((uint64_t)gb + c4 > bcap) wsum[18] = 1;
+        atomicMax(&wsum[19], gb + c4);
+      }
+      gbase[tid] = tid * bcap + gb;  // < 2^32: checked by the launcher
+    }
+    __syncthreads();
+    if (!wsum[18]) {
+      const int lane = lane_id();
+      for (int b = tid >> 6; b < nb; b += 16) {
+        const uint32_t o = roff[b], cnt = roff[b + 1] - o;
+        const uint32_t cr = (cnt + (kCG - 1)) & ~(uint32_t)(kCG - 1);
+        uint4* dst = (uint4*)(out + gbase[b]);  // 32-byte aligned run, whole granules
+        for (uint32_t j = 2 * lane; j < cr; j += 128) {
+          const uint2 a = j < cnt ? rbuf[o + j] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+          const uint2 c = j + 1 < cnt ? rbuf[o + j + 1] : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+          dst[j >> 1] = make_uint4(a.x, a.y, c.x, c.y);
+        }
+      }
+    }
+    // No barrier here: the next round only adds to rcnt (cleared above) until its first barrier.
+  }
+  __syncthreads();
+  const bool any_ovf = wsum[18] != 0;
+  const uint32_t nacc = wsum[17];
+
+  int64_t qmin = qmin32 == 0xFFFFFFFFu && qmax32 == 0 ? INT64_MAX : (int64_t)qmin32;
+  int64_t qmax = qmin == INT64_MAX ? INT64_MIN : (int64_t)qmax32;
+  tmax = block_reduce_i64(tmax, lred, 0);
+  qmin = block_reduce_i64(qmin, lred, 1);
+  qmax = block_reduce_i64(qmax, lred, 0);
+  pmask = (uint32_t)block_reduce_i64(pmask, lred, 3);
+  const int64_t nlate_g = late_idx ? 0 : block_reduce_i64(nlate, lred, 2);
+  const int64_t fl = (any_ovf ? 1 : 0) | block_reduce_i64(flags, lred, 3);
+  if (threadIdx.x == 0) {
+    if (wsum[19])
+      atomicMax((unsigned long long*)&stats[kStatMaxBucket], (unsigned long long)wsum[19]);
+    atomicMax((long long*)&stats[kStatMaxTs], (long long)tmax);
+    if (nacc) {
+      atomicMin((long long*)&stats[kStatMinPane], (long long)qmin);
+      atomicMax((long long*)&stats[kStatMaxPane], (long long)qmax);
+      atomicAdd((unsigned long long*)&stats[kStatAccepted], (unsigned long long)nacc);
+      if (pmask) atomicOr((unsigned long long*)&stats[kStatPaneMask], (unsigned long long)pmask);
+    }
+    if (nlate_g) atomicAdd((unsigned long long*)&stats[kStatLate], (unsigned long long)nlate_g);
+    if (fl) atomicOr((unsigned long long*)&stats[kStatOverflow], (unsigned long long)fl);
+  }
+}
+
 // Step prologue: zero the bucket cursors and reset the stats block (one launch instead of two
 // memsets + a host copy).
 __global__ __launch_bounds__(256) void step_begin_kernel(uint32_t* __restrict__ cursor, int nb,
@@ -4843,25 +5163,81 @@ __global__ __launch_bounds__(kSplitThreads) void partition_split_kernel(
     atomicOr((unsigned long long*)&stats[kStatOverflow], 1ull);  // bucket overflow: redo
 }
 
+// PAIR loads (two events per lane, 16-byte ts / value loads) need 16-byte aligned columns
+// (8-byte for int32 keys); a misaligned view takes the lane-strided kernel.
+static bool pair_aligned(const uint64_t* keys, const int64_t* ts, const uint64_t* vals, bool key32) {
+  return ((uintptr_t)ts % 16 == 0) && ((uintptr_t)vals % 16 == 0) &&
+         ((uintptr_t)keys % (key32 ? 8 : 16) == 0) && kPairEnv;
+}
+
+// The one-pass kernel's plan: one destination, <= 512 buckets, runs that its 16-byte stores of
+// whole granules can address.
+static bool onepass_ok(const PartPlan& plan, const void* out) {
+  return plan.rec_words == 1 && plan.nranks == 1 && plan.nsub_log2 >= 0 &&
+         (1 << plan.nsub_log2) <= kCMaxNb && plan.bucket_cap % kCG == 0 &&
+         (uintptr_t)out % 16 == 0 &&
+         ((uint64_t)plan.bucket_cap << plan.nsub_log2) < (1ull << 32);
+}
+
+// One-pass partition with rounds of 1024 * RU records; `chunk` events per workgroup.
+template <int RU>
+void launch_onepass(const uint64_t* keys, const int64_t* ts, const uint64_t* vals, int64_t n,
+                    int64_t chunk, int blocks, const PartPlan& plan, uint32_t* cursor, Rec* out,
+                    int64_t* stats, uint32_t* late_idx, uint32_t late_cap, intptr_t stream) {
+  PartPlan pl = plan;
+  if (!kFastEnv) pl.ablate |= 8u;  // wave-vote fast path off
+  // PAIR loads also need even group boundaries.
+  const bool pair = pair_aligned(keys, ts, vals, plan.key32) && (blocks == 1 || chunk % 2 == 0);
+#define MXS_ONEPASS(K32_, PAIR_)                                                                \
+  do {                                                                                          \
+    auto kfn = partition_onepass_kernel<1, RU, K32_, PAIR_>;                                    \
+    static bool attr = false;                                                                   \
+    if (!attr) {                                                                                \
+      HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                    (int)onepass_lds(RU)));                                     \
+      attr = true;                                                                              \
+    }                                                                                           \
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(1024), onepass_lds(RU), (hipStream_t)stream,      \
+                       keys, ts, vals, n, chunk, pl, cursor, reinterpret_cast<uint2*>(out),      \
+                       stats, late_idx, late_cap);                                               \
+  } while (0)
+  if (plan.key32) {
+    if (pair) MXS_ONEPASS(true, true);
+    else MXS_ONEPASS(true, false);
+  } else {
+    if (pair) MXS_ONEPASS(false, true);
+    else MXS_ONEPASS(false, false);
+  }
+#undef MXS_ONEPASS
+  HIP_CHECK(hipGetLastError());
+}
+
 template <bool ONE, int RB>
 void dispatch_compact(const uint64_t* keys, const int64_t* ts, const uint64_t* vals,
                       const int32_t* jhash_tab, int64_t n, const PartPlan& plan,
                       const int32_t* kg_dest, uint32_t* cursor, Rec* out, int64_t* stats,
-                      uint32_t* late_idx, uint32_t late_cap, intptr_t stream) {
+                      uint32_t* late_idx, uint32_t late_cap, intptr_t stream,
+                      bool allow_onepass = true) {
   // 4096-record rounds, up to 64K events per workgroup (one group per CU: 86 KB of LDS),
   // i.e. one workgroup per CU at 16M events. Against 2048-record rounds / 32K events at two
   // groups per CU (kbench, profiles/r1_partition_rounds.md): 227 -> 198 us. Longer bucket
   // runs per group and bigger rounds cut the partial-sector writes and the per-group
   // reservation work; fewer, larger groups beat the higher occupancy.
-  const int64_t per = std::min<int64_t>(65536, std::max<int64_t>(4096, (n + 255) / 256));
-  const int blocks = grid_for(n, per, 4096);
-  int64_t chunk = (n + blocks - 1) / blocks;
-  // PAIR loads (two events per lane, 16-byte ts / value loads) need even group boundaries and
-  // 16-byte aligned columns (8-byte for int32 keys); a misaligned view takes the lane-strided
-  // kernel.
-  const bool pair = ((uintptr_t)ts % 16 == 0) && ((uintptr_t)vals % 16 == 0) &&
-                    ((uintptr_t)keys % (plan.key32 ? 8 : 16) == 0) && kPairEnv;
+  const PartGrid grid = compact_part_grid(n);
+  const int blocks = grid.blocks;
+  int64_t chunk = grid.chunk;
+  const bool pair = pair_aligned(keys, ts, vals, plan.key32);
   if (pair) chunk = (chunk + 1) & ~(int64_t)1;
+  if constexpr (ONE && RB == 8) {
+    // One pass over the events (profiles/partition_onepass.md). MXS_PART_ONEPASS=0: the
+    // two-pass kernel below (A/B knob).
+    static const bool onepass = getenv_int("MXS_PART_ONEPASS", 1) != 0;
+    if (onepass && allow_onepass && onepass_ok(plan, out)) {
+      launch_onepass<kOnePassRound / 1024>(keys, ts, vals, n, chunk, blocks, plan, cursor, out,
+                                           stats, late_idx, late_cap, stream);
+      return;
+    }
+  }
   PartPlan pl = plan;
   if (!kFastEnv) pl.ablate |= 8u;  // wave-vote fast path off
 #define MXS_COMPACT(K32_, PAIR_)                                                                \
@@ -4994,10 +5370,40 @@ void partition(const uint64_t* keys, const int64_t* ts, const uint64_t* vals,
 void partition_variant(const uint64_t* keys, const int64_t* ts, const uint64_t* vals,
                        const int32_t* jhash_tab, int64_t n, const PartPlan& plan,
                        const int32_t* kg_dest, uint32_t* cursor, Rec* out, int64_t* stats,
-                       uint32_t* late_idx, uint32_t late_cap, intptr_t stream, int variant) {
+                       uint32_t* late_idx, uint32_t late_cap, intptr_t stream, int variant,
+                       int64_t events_per_group) {
   if (n <= 0) return;
   const int nb = plan.nranks << plan.nsub_log2;
   if (nb > 16384) throw std::runtime_error("partition: too many buckets (max 16384)");
+  if (variant >= 20 && variant <= 23) {
+    // 8-byte records, one destination: 20 = the two-pass compact kernel, 21 / 23 = the one-pass
+    // kernel with rounds of 8192 / 16384 records (22, 12288 records, spilled registers and was
+    // the slowest: profiles/partition_onepass.md). events_per_group > 0 sets the one-pass
+    // workgroups' chunk (several rounds per group at small n); 0: production grid.
+    if (!onepass_ok(plan, out)) throw std::runtime_error("narrow one-destination variant: plan");
+    if (variant == 20) {
+      dispatch_compact<true, 8>(keys, ts, vals, jhash_tab, n, plan, kg_dest, cursor, out, stats,
+                                late_idx, late_cap, stream, false);
+      return;
+    }
+    PartGrid g = compact_part_grid(n);
+    if (events_per_group > 0) {
+      if ((n + events_per_group - 1) / events_per_group > 4096)
+        throw std::runtime_error("one-pass variant: more than 4096 groups");
+      g.blocks = (int)((n + events_per_group - 1) / events_per_group);
+      g.chunk = events_per_group;
+    } else if (pair_aligned(keys, ts, vals, plan.key32)) {
+      g.chunk = (g.chunk + 1) & ~(int64_t)1;
+    }
+#define MXS_PART_ONEPASS_V(RU)                                                                 \
+  launch_onepass<RU>(keys, ts, vals, n, g.chunk, g.blocks, plan, cursor, out, stats, late_idx,  \
+                     late_cap, stream)
+    if (variant == 21) MXS_PART_ONEPASS_V(8);
+    else if (variant == 23) MXS_PART_ONEPASS_V(16);
+    else throw std::runtime_error("partition: unknown variant");
+#undef MXS_PART_ONEPASS_V
+    return;
+  }
   // 64K events per 1024-thread workgroup: one workgroup per CU at 16M events, bucket runs of
   // >= 32 records, and nb global reservations per workgroup instead of per 8K events.
   int blocks = grid_for(n, 65536, 1024);

@@ -559,6 +559,34 @@ struct PartPlan {
   uint32_t* scratch_cursor;  // [512] coarse fills
 };
 
+// Geometry of the GPU compact partitions, shared by the kernels' launcher and the host's bucket
+// capacity (WindowStep::alloc_buckets). A workgroup takes a chunk of up to kPartGroupEvents
+// events; every reservation of a bucket run is rounded up to kPartGranule records (32 bytes of
+// 8-byte records), so each costs at most kPartGranule - 1 padding holes. The two-pass kernels
+// reserve once per workgroup and bucket, the one-pass kernel once per round of kOnePassRound
+// records.
+constexpr int kPartGranule = 4;
+constexpr int kOnePassRound = 16384;
+constexpr int64_t kPartGroupEvents = 65536;
+struct PartGrid {
+  int blocks;
+  int64_t chunk;  // events per workgroup
+};
+inline PartGrid compact_part_grid(int64_t n) {
+  int64_t per = (n + 255) / 256;
+  per = per < 4096 ? 4096 : per > kPartGroupEvents ? kPartGroupEvents : per;
+  int64_t g = (n + per - 1) / per;
+  g = g < 1 ? 1 : g > 4096 ? 4096 : g;
+  return PartGrid{(int)g, (n + g - 1) / g};
+}
+// Upper bound of the padding holes one bucket receives from a step of n events (one-pass
+// kernel, production grid; the launcher may round a chunk up to an even size).
+inline int64_t onepass_hole_bound(int64_t n) {
+  const PartGrid g = compact_part_grid(n);
+  const int64_t rounds = (((g.chunk + 1) & ~(int64_t)1) + kOnePassRound - 1) / kOnePassRound;
+  return (int64_t)(kPartGranule - 1) * g.blocks * rounds;
+}
+
 // Sub-table of a key: a 32-bit multiplicative hash of both key halves (3 32-bit multiplies).
 // Independent of the slot hash (low bits of mix64) and about half the VALU of a second mix64 —
 // the partition pass evaluates it twice per event and is VALU-bound.

@@ -418,9 +418,13 @@ void WindowStep::alloc_buckets(int64_t capacity, double slack) {
   slack_ = slack;
   const double per = (double)capacity / nbuckets_;
   // The GPU partition pads every workgroup's run to whole 8-record groups (<= 7 holes per bucket
-  // and workgroup, <= 1024 workgroups): capacity is a multiple of 8 with that slack.
-  const int64_t nblk = std::min<int64_t>(1024, std::max<int64_t>(1, (capacity + 65535) / 65536));
-  const int64_t cap = (int64_t)(per * slack + 6 * std::sqrt(std::max(per, 1.0)) + 64) + 8 * nblk;
+  // and workgroup, <= 1024 workgroups): capacity is a multiple of 8 with that slack. The one-pass
+  // narrow partition reserves once per round instead (onepass_hole_bound, from the kernel's own
+  // geometry): the slack covers whichever is larger, so a full batch never overflows on holes.
+  const int64_t nblk = std::min<int64_t>(
+      1024, std::max<int64_t>(1, (capacity + kPartGroupEvents - 1) / kPartGroupEvents));
+  const int64_t holes = std::max<int64_t>(8 * nblk, gpu_ ? onepass_hole_bound(capacity) : 0);
+  const int64_t cap = (int64_t)(per * slack + 6 * std::sqrt(std::max(per, 1.0)) + 64) + holes;
   bucket_cap_ = (cap + 7) & ~(int64_t)7;
   const size_t words = (size_t)nbuckets_ * bucket_cap_ * 3;
   const int dk = gpu_ ? 1 : 0;
