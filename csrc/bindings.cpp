@@ -566,6 +566,21 @@ PYBIND11_MODULE(_mxs_native, m) {
                       P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot), P<uint32_t>(on), out_cap,
                       abits, shift, stream, count_n);
   });
+  m.def("gpu_rolling_slide_scan", [](int agg, intptr_t sk, intptr_t vals, intptr_t n_in,
+                                     intptr_t heads, intptr_t n_heads, int64_t max_segments,
+                                     intptr_t acc_g, intptr_t cnt_g, intptr_t ord_g,
+                                     intptr_t ring_g, intptr_t keys_g, std::vector<int32_t> code,
+                                     std::vector<double> consts, intptr_t ok, intptr_t ov,
+                                     intptr_t ot, intptr_t oc, intptr_t on, uint32_t out_cap,
+                                     int abits, int shift, intptr_t stream, uint32_t size,
+                                     uint32_t slide) {
+    gpu::rolling_slide_scan(agg, P<int64_t>(sk), P<uint64_t>(vals), P<uint32_t>(n_in),
+                            P<uint32_t>(heads), P<uint32_t>(n_heads), max_segments,
+                            P<uint64_t>(acc_g), P<uint32_t>(cnt_g), P<uint64_t>(ord_g),
+                            P<uint64_t>(ring_g), P<uint64_t>(keys_g), make_prog(code, consts),
+                            P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot), P<uint32_t>(oc),
+                            P<uint32_t>(on), out_cap, abits, shift, stream, size, slide);
+  });
   m.def("gpu_session_lookup", [](intptr_t recs, intptr_t counts, int nsrc, int nsub, uint32_t bcap,
                                  int cap_log2, intptr_t keys_g, intptr_t spill_set,
                                  uint32_t spill_mask, int spill_any, intptr_t sk, intptr_t vals,
@@ -1270,6 +1285,21 @@ PYBIND11_MODULE(_mxs_native, m) {
                       P<uint64_t>(keys_g), P<uint64_t>(acc_g), P<uint32_t>(cnt_g),
                       P<uint32_t>(flags), f, P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot),
                       P<uint32_t>(on), out_cap, count_n);
+  });
+  m.def("cpu_rolling_slide_rows", [](intptr_t recs, intptr_t counts, int nsrc, int nsub,
+                                     uint32_t bcap, int cap_log2, int agg, intptr_t keys_g,
+                                     intptr_t acc_g, intptr_t cnt_g, intptr_t ord_g,
+                                     intptr_t ring_g, intptr_t flags, std::vector<int32_t> code,
+                                     std::vector<double> consts, intptr_t ok, intptr_t ov,
+                                     intptr_t ot, intptr_t oc, intptr_t on, uint32_t out_cap,
+                                     uint32_t size, uint32_t slide) {
+    ExprProg f = make_prog(code, consts);
+    py::gil_scoped_release nogil;
+    cpu::rolling_slide_rows(P<Rec>(recs), P<uint32_t>(counts), nsrc, nsub, bcap, cap_log2, agg,
+                            P<uint64_t>(keys_g), P<uint64_t>(acc_g), P<uint32_t>(cnt_g),
+                            P<uint64_t>(ord_g), P<uint64_t>(ring_g), P<uint32_t>(flags), f,
+                            P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot), P<uint32_t>(oc),
+                            P<uint32_t>(on), out_cap, size, slide);
   });
   m.def("cpu_expr_filter_compact", [](intptr_t x, int64_t n, std::vector<int32_t> code,
                                       std::vector<double> consts, intptr_t idx, intptr_t total) {

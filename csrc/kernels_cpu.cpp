@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cstring>
 #include <functional>
+#include <numeric>
 #include <stdexcept>
 #include <thread>
 #include <vector>
@@ -394,6 +395,76 @@ void rolling_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub, u
           ++n;
         }
         if (count_n && cnt_g[gi] == count_n) cnt_g[gi] = 0;  // window purged
+      }
+    }
+  }
+  *out_n = n;
+}
+
+// Sliding count windows countWindow(size, slide), the oracle of gpu::rolling_slide_scan. Per key:
+// every element folds into the open pane (acc_g, cnt_g) left to right; a full pane (gcd(size,
+// slide) elements) goes to ring_g[slot * ppw + pane number % ppw]; at every ordinal that is a
+// multiple of slide the last ppw existing panes are combined oldest first.
+void rolling_slide_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub,
+                        uint32_t bucket_cap, int cap_log2, int agg, uint64_t* keys_g,
+                        uint64_t* acc_g, uint32_t* cnt_g, uint64_t* ord_g, uint64_t* ring_g,
+                        uint32_t* flags, const ExprProg& filt, uint64_t* out_key,
+                        uint64_t* out_val, int64_t* out_tag, uint32_t* out_cnt, uint32_t* out_n,
+                        uint32_t out_cap, uint32_t size, uint32_t slide) {
+  if (size < 1 || slide < 1 || size >= (1u << 31) || slide >= (1u << 31))
+    throw std::invalid_argument("rolling_slide_rows: size / slide out of range");
+  const uint32_t pane = std::gcd(size, slide), ppw = size / pane;
+  if (ppw > kSlideMaxPanes)
+    throw std::invalid_argument("rolling_slide_rows: more than 64 panes per window");
+  const uint32_t mask = (1u << cap_log2) - 1;
+  uint32_t n = *out_n;
+  for (int sub = 0; sub < nsub; ++sub) {
+    uint64_t* keys = keys_g + ((size_t)sub << cap_log2);
+    bool inserted = false;
+    for (int src = 0; src < nsrc; ++src) {
+      const uint32_t c = std::min(counts[(size_t)src * nsub + sub], bucket_cap);
+      const Rec* seg = recs + ((size_t)src * nsub + sub) * bucket_cap;
+      for (uint32_t e = 0; e < c; ++e) {
+        const Rec& r = seg[e];
+        if (r.t == 0xFFFFFFFFu) continue;
+        const uint32_t s = probe_insert(keys, r.key, mask, &inserted);
+        if (s == kNoSlot) {
+          flags[0] |= 1u;
+          continue;
+        }
+        const size_t gi = ((size_t)sub << cap_log2) + s;
+        uint64_t* ring = ring_g + gi * ppw;
+        const uint64_t v = agg_lift(agg, r.val);
+        acc_g[gi] = cnt_g[gi] ? agg_combine(agg, acc_g[gi], v) : v;
+        cnt_g[gi] += 1;
+        const uint64_t ord = ++ord_g[gi];
+        if (cnt_g[gi] < pane) continue;
+        const uint64_t done = ord / pane;  // panes completed, this one included
+        ring[(done - 1) % ppw] = acc_g[gi];
+        cnt_g[gi] = 0;
+        if (ord % slide) continue;
+        const uint64_t first = done > ppw ? done - ppw : 0;
+        uint64_t w = ring[first % ppw];
+        for (uint64_t p = first + 1; p < done; ++p) w = agg_combine(agg, w, ring[p % ppw]);
+        const uint32_t wcount = (uint32_t)std::min<uint64_t>(ord, size);
+        bool emit = true;
+        if (filt.ncode) {
+          double vars[kExprVars] = {0};
+          vars[0] = agg_result_f64(agg, w, wcount);
+          vars[1] = (double)wcount;
+          vars[4] = (double)r.key;
+          vars[5] = (double)(int64_t)w;
+          vars[6] = vars[0];
+          emit = expr_eval(filt, vars) != 0.0;
+        }
+        if (!emit) continue;
+        if (n < out_cap) {
+          out_key[n] = r.key;
+          out_val[n] = agg == AGG_COUNT ? (uint64_t)wcount : w;
+          out_tag[n] = ((int64_t)src << 32) | r.aux;
+          out_cnt[n] = wcount;
+        }
+        ++n;
       }
     }
   }

@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <numeric>
 #include <stdexcept>
 #include <string>
 
@@ -3200,6 +3201,163 @@ __global__ __launch_bounds__(256) void rolling_scan_kernel(
   }
 }
 
+// Sliding count windows (countWindow(size, slide): GlobalWindows + CountEvictor(size) +
+// CountTrigger(slide)) over panes of ordinals: pane = gcd(size, slide) elements, ppw = size / pane
+// panes per window (<= 64). Per slot: acc_g/cnt_g hold the open pane, ord_g the key's 64-bit
+// element ordinal, ring_g[slot * ppw + (p % ppw)] the partial of completed pane p. One wave walks
+// a key segment; lane j keeps ring entry j in a register for the whole segment. Per 64-element
+// chunk: the tumbling kernel's segmented scan with a start at every pane boundary; a lane whose
+// ordinal is a multiple of `slide` fires and combines, oldest first, the last ppw existing
+// panes -- those from before the chunk out of the ring register, those completed earlier in the
+// chunk out of the completing lanes' scan results (both read with per-lane-source shuffles in a
+// loop of wave-uniform trip count). The chunk's panes enter the ring only after every firing
+// lane has read it. Chunk-relative quantities are 32-bit; only the ordinal itself is 64-bit.
+template <int AGG>
+__global__ __launch_bounds__(256) void rolling_slide_scan_kernel(
+    const int64_t* __restrict__ sk, const uint64_t* __restrict__ vals,
+    const uint32_t* __restrict__ n_in, const uint32_t* __restrict__ heads,
+    const uint32_t* __restrict__ n_heads, uint64_t* __restrict__ acc_g,
+    uint32_t* __restrict__ cnt_g, uint64_t* __restrict__ ord_g, uint64_t* __restrict__ ring_g,
+    const uint64_t* __restrict__ keys_g, ExprProg filt, uint64_t* __restrict__ out_key,
+    uint64_t* __restrict__ out_val, int64_t* __restrict__ out_tag, uint32_t* __restrict__ out_cnt,
+    uint32_t* __restrict__ out_n, uint32_t out_cap, int abits, int shift, uint32_t size,
+    uint32_t slide, uint32_t pane, uint32_t ppw) {
+  extern __shared__ __attribute__((aligned(16))) double rsm[];  // VM columns [8 + depth][256]
+  LdsCol vars{rsm + threadIdx.x, 256};
+  LdsCol stack{rsm + kExprVars * 256 + threadIdx.x, 256};
+  const uint32_t n = *n_in, nh = *n_heads;
+  const uint32_t lane = (uint32_t)lane_id();
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t h = wave; h < nh; h += nwaves) {  // wave-uniform loop
+    const uint32_t start = heads[h];
+    const uint64_t slot = (uint64_t)(sk[start] >> shift);
+    uint32_t end = start + 1;
+    for (;;) {  // segment end, as in rolling_scan_kernel
+      const uint32_t i = end + lane;
+      const bool same = i < n && (uint64_t)(sk[i] >> shift) == slot && sk[i] != INT64_MAX;
+      const unsigned long long m = __ballot(!same);
+      if (m) {
+        end += (uint32_t)__ffsll((long long)m) - 1;
+        break;
+      }
+      end += 64;
+    }
+    uint64_t ord = ord_g[slot];  // elements of this key so far
+    uint64_t npanes;             // panes completed so far
+    uint32_t c, os;              // fill of the open pane; ordinal mod slide
+    if ((ord >> 32) == 0) {      // wave-uniform: 32-bit division while the ordinal fits
+      npanes = (uint32_t)ord / pane;
+      c = (uint32_t)ord % pane;
+      os = (uint32_t)ord % slide;
+    } else {
+      npanes = ord / pane;
+      c = (uint32_t)(ord % pane);
+      os = (uint32_t)(ord % slide);
+    }
+    uint32_t rp = (uint32_t)(npanes % ppw);              // ring position of the next pane
+    uint32_t np = (uint32_t)(npanes < ppw ? npanes : ppw);  // panes the ring holds
+    uint32_t full = (uint32_t)(ord < size ? ord : size);   // min(ordinal, size)
+    uint64_t carry = c ? acc_g[slot] : 0;
+    bool have = c != 0;
+    uint64_t ring = lane < ppw ? ring_g[slot * ppw + lane] : 0;
+    const uint64_t key = keys_g[slot];
+    for (uint32_t b0 = start; b0 < end; b0 += 64) {
+      const uint32_t i = b0 + lane;
+      const bool in = i < end;
+      const uint32_t nin = (end - b0) < 64 ? (end - b0) : 64;
+      uint64_t v = in ? agg_lift(AGG, vals[i]) : 0;
+      int f = (c + lane) % pane == 0;
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t y = __shfl_up(v, o);
+        const int g = __shfl_up(f, o);
+        if ((int)lane >= o && in && !f) {
+          v = roll_combine<AGG>(y, v);
+          f = g;
+        }
+      }
+      const uint64_t post = have && !f ? roll_combine<AGG>(carry, v) : v;
+      // kc: panes completed in this chunk up to and including this lane; local pane k completes
+      // at lane (k + 1) * pane - c - 1.
+      const uint32_t kc = (c + lane + 1) / pane;
+      const bool fire = in && (os + lane + 1) % slide == 0;
+      uint64_t w = post;
+      if (__ballot(fire)) {
+        const uint32_t kl = kc < ppw ? kc : ppw;               // panes taken from this chunk
+        const uint32_t nr = ppw - kl < np ? ppw - kl : np;     // panes taken from the ring
+        const uint32_t tot = fire ? nr + kl : 0;
+        uint32_t rpos = rp + ppw - nr;                         // oldest ring pane wanted
+        rpos = rpos >= ppw ? rpos - ppw : rpos;
+        uint32_t llane = (kc - kl + 1) * pane - c - 1;         // oldest local pane wanted
+        const uint32_t kall = (c + nin) / pane;
+        const uint32_t trips = np + kall < ppw ? np + kall : ppw;  // wave-uniform
+        for (uint32_t t = 0; t < trips; ++t) {
+          const bool from_ring = t < nr;
+          const uint64_t xr = __shfl(ring, (int)(rpos & 63u));
+          const uint64_t xl = __shfl(post, (int)(llane & 63u));
+          const uint64_t x = from_ring ? xr : xl;
+          if (t < tot) w = t ? roll_combine<AGG>(w, x) : x;
+          if (from_ring) {
+            rpos = rpos + 1 == ppw ? 0 : rpos + 1;
+          } else {
+            llane += pane;
+          }
+        }
+      }
+      const uint32_t pcount = full + lane + 1 < size ? full + lane + 1 : size;
+      bool emit = fire;
+      if (fire && filt.ncode) {
+        vars.set(0, agg_result_f64(AGG, w, pcount));
+        vars.set(1, (double)pcount);
+        vars.set(4, (double)key);
+        vars.set(5, (double)(int64_t)w);
+        vars.set(6, agg_result_f64(AGG, w, pcount));
+        emit = expr_eval_t(filt, stack, vars) != 0.0;
+      }
+      const unsigned long long m = __ballot(emit);
+      uint32_t wb = 0;
+      if (lane == 0 && m) wb = atomicAdd(out_n, (uint32_t)__popcll(m));
+      wb = __shfl(wb, 0);
+      if (emit) {
+        const uint32_t q = wb + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (q < out_cap) {
+          out_key[q] = key;
+          out_val[q] = AGG == AGG_COUNT ? (uint64_t)pcount : w;
+          const int64_t k = sk[i];
+          const int64_t srcv = (k >> abits) & (((int64_t)1 << (shift - abits)) - 1);
+          out_tag[q] = (srcv << 32) | (k & (((int64_t)1 << abits) - 1));  // src << 32 | arrival
+          out_cnt[q] = pcount;
+        }
+      }
+      // The chunk's completed panes enter the ring: position j takes the newest local pane k
+      // with (rp + k) % ppw == j.
+      const uint32_t kall = (c + nin) / pane;
+      {
+        const uint32_t k0 = lane >= rp ? lane - rp : lane + ppw - rp;  // lanes >= ppw: unused
+        const bool take = lane < ppw && k0 < kall;
+        const uint32_t k = take ? k0 + (kall - 1 - k0) / ppw * ppw : 0;
+        const uint32_t src = (k + 1) * pane - c - 1;
+        const uint64_t x = __shfl(post, (int)(take ? src : 0u));
+        if (take) ring = x;
+      }
+      carry = __shfl(post, (int)nin - 1);
+      have = true;
+      np = np + kall < ppw ? np + kall : ppw;
+      rp = (rp + kall) % ppw;
+      c = (c + nin) % pane;
+      os = (os + nin) % slide;
+      full = full + nin < size ? full + nin : size;
+      ord += nin;
+    }
+    if (lane == 0) {
+      acc_g[slot] = carry;
+      cnt_g[slot] = c;
+      ord_g[slot] = ord;
+    }
+    if (lane < ppw) ring_g[slot * ppw + lane] = ring;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Session windows on the GPU (BASELINE config 5). Per key slot: up to kSess sessions (SoA:
 // start, end, acc, cnt, flags) + due time (min over sessions of maxTs, or cleanup time once
@@ -5994,6 +6152,33 @@ void rolling_scan(int agg, const int64_t* sk, const int64_t* perm, const uint64_
     MXS_R(AGG_AVG_I64) MXS_R(AGG_AVG_F64)
 #undef MXS_R
     default: throw std::runtime_error("rolling_scan: unsupported aggregate");
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void rolling_slide_scan(int agg, const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
+                        const uint32_t* heads, const uint32_t* n_heads, int64_t max_segments,
+                        uint64_t* acc_g, uint32_t* cnt_g, uint64_t* ord_g, uint64_t* ring_g,
+                        const uint64_t* keys_g, const ExprProg& filt, uint64_t* out_key,
+                        uint64_t* out_val, int64_t* out_tag, uint32_t* out_cnt, uint32_t* out_n,
+                        uint32_t out_cap, int abits, int shift, intptr_t stream, uint32_t size,
+                        uint32_t slide) {
+  check_roll_layout(abits, shift);
+  if (size < 1 || slide < 1 || size >= (1u << 31) || slide >= (1u << 31))
+    throw std::invalid_argument("rolling_slide_scan: size / slide out of range");
+  const uint32_t pane = std::gcd(size, slide), ppw = size / pane;
+  if (ppw > kSlideMaxPanes)
+    throw std::invalid_argument("rolling_slide_scan: more than 64 panes per window");
+  const int grid = grid_for(max_segments * 64, 256, 4096);
+  const size_t lds = (size_t)(kExprVars + filt.depth) * 256 * sizeof(double);
+  hipStream_t s = (hipStream_t)stream;
+  switch (agg) {
+#define MXS_R(A) case A: hipLaunchKernelGGL(rolling_slide_scan_kernel<A>, dim3(grid), dim3(256), lds, s, sk, vals, n_in, heads, n_heads, acc_g, cnt_g, ord_g, ring_g, keys_g, filt, out_key, out_val, out_tag, out_cnt, out_n, out_cap, abits, shift, size, slide, pane, ppw); break;
+    MXS_R(AGG_SUM_I64) MXS_R(AGG_SUM_F64) MXS_R(AGG_MIN_I64) MXS_R(AGG_MAX_I64)
+    MXS_R(AGG_MIN_F64) MXS_R(AGG_MAX_F64) MXS_R(AGG_COUNT)
+    MXS_R(AGG_AVG_I64) MXS_R(AGG_AVG_F64)
+#undef MXS_R
+    default: throw std::runtime_error("rolling_slide_scan: unsupported aggregate");
   }
   HIP_CHECK(hipGetLastError());
 }

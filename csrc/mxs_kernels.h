@@ -187,6 +187,8 @@ inline const char* topn_check(const TopnCols& in, const TopnPlan& p, const TopnC
 }
 
 constexpr int64_t kRollHistMaxSlots = 16384;  // LDS running-count table of the emit pass
+// Sliding count windows: panes per window a key's ring may hold (one register per lane of a wave).
+constexpr uint32_t kSlideMaxPanes = 64;
 
 // Order-preserving compaction tiles (filter_mask / line_starts / ingest masks): a 256-thread
 // workgroup owns kFcTile rows, one 64-bit ballot word per wave and item.
@@ -444,6 +446,17 @@ void rolling_scan(int agg, const int64_t* sk, const int64_t* perm, const uint64_
                   const ExprProg& filt, uint64_t* out_key, uint64_t* out_val, int64_t* out_tag,
                   uint32_t* out_n, uint32_t out_cap, int abits, int shift, intptr_t stream,
                   uint32_t count_n = 0);
+// Sliding count windows countWindow(size, slide) over the same sorted batch: pane = gcd(size,
+// slide) elements, ppw = size / pane <= kSlideMaxPanes panes per window. ord_g[nslots] is each
+// key's element ordinal, ring_g[nslots * ppw] the completed pane partials (pane p of a slot at
+// p % ppw), acc_g / cnt_g the open pane. out_cnt is the window's element count, min(ordinal, size).
+void rolling_slide_scan(int agg, const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
+                        const uint32_t* heads, const uint32_t* n_heads, int64_t max_segments,
+                        uint64_t* acc_g, uint32_t* cnt_g, uint64_t* ord_g, uint64_t* ring_g,
+                        const uint64_t* keys_g, const ExprProg& filt, uint64_t* out_key,
+                        uint64_t* out_val, int64_t* out_tag, uint32_t* out_cnt, uint32_t* out_n,
+                        uint32_t out_cap, int abits, int shift, intptr_t stream, uint32_t size,
+                        uint32_t slide);
 // idle: this partition is idle (red[2] = +inf: no say in the MIN watermark); host_red: also
 // store the reduced vector into this pinned host buffer (one rank: no all-reduce in between, so
 // the step's host read needs no separate copy).
@@ -563,6 +576,15 @@ void rolling_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub, u
                   int cap_log2, int agg, uint64_t* keys_g, uint64_t* acc_g, uint32_t* cnt_g,
                   uint32_t* flags, const ExprProg& filt, uint64_t* out_key, uint64_t* out_val,
                   int64_t* out_tag, uint32_t* out_n, uint32_t out_cap, uint32_t count_n = 0);
+// The sliding count-window twin of gpu::rolling_slide_scan (same state layout, and the combine
+// order the kernel has to reproduce: elements fold into the open pane left to right, panes
+// combine oldest first at a firing).
+void rolling_slide_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub,
+                        uint32_t bucket_cap, int cap_log2, int agg, uint64_t* keys_g,
+                        uint64_t* acc_g, uint32_t* cnt_g, uint64_t* ord_g, uint64_t* ring_g,
+                        uint32_t* flags, const ExprProg& filt, uint64_t* out_key,
+                        uint64_t* out_val, int64_t* out_tag, uint32_t* out_cnt, uint32_t* out_n,
+                        uint32_t out_cap, uint32_t size, uint32_t slide);
 void step_finish(const int64_t* stats, int64_t* local_maxts, int64_t bound, int32_t event_mode,
                  int64_t proc_now, int64_t* red, const uint32_t* flags, int32_t idle = 0,
                  int32_t fill_word = 0, const uint32_t* cursor = nullptr, int nb = 0);

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 #include "mxs_check.h"
@@ -157,6 +158,53 @@ int main() {
                          out_keys.data(), out_vec.data(), out_cnt.data(), &vn);
     if (vn != out_n[0]) return fail("vector and scalar windows disagree on live keys");
     fired_through = qmin;
+  }
+  {
+    // Sliding count windows (rolling_slide_rows): the pane ring at its 64-pane limit (64, 1), a
+    // 65-element pane (130, 65), slide > size (3, 5); two source
+    // buckets per sub-table (one full to its capacity), hole records, three batches.
+    const int s_nsub = 2, s_cap_log2 = 4, s_nsrc = 2;
+    const uint32_t s_bcap = 257;
+    const size_t s_slots = (size_t)s_nsub << s_cap_log2;
+    const uint32_t shapes[3][2] = {{64, 1}, {130, 65}, {3, 5}};
+    for (const auto& sh : shapes) {
+      const uint32_t size = sh[0], slide = sh[1], ppw = size / std::gcd(size, slide);
+      std::vector<uint64_t> sk(s_slots, kEmptyKey), sa(s_slots), so(s_slots), sr(s_slots * ppw);
+      std::vector<uint32_t> sc(s_slots), sflags(4), scount((size_t)s_nsrc * s_nsub);
+      std::vector<Rec> srecs((size_t)s_nsrc * s_nsub * s_bcap);
+      const uint32_t ocap = 300;  // smaller than the (64, 1) row count: the clamp is exercised
+      std::vector<uint64_t> ok(ocap), ov(ocap);
+      std::vector<int64_t> ot(ocap);
+      std::vector<uint32_t> oc(ocap), on(1);
+      uint64_t rows = 0;
+      for (int step = 0; step < 3; ++step) {
+        for (int b = 0; b < s_nsrc * s_nsub; ++b) {
+          const uint32_t c = b == 0 ? s_bcap : 100 + 37 * (uint32_t)b;
+          scount[b] = c;
+          for (uint32_t e = 0; e < c; ++e) {
+            Rec& r = srecs[(size_t)b * s_bcap + e];
+            r.key = (uint64_t)(b % s_nsub) * 1000 + e % 5;
+            r.val = (uint64_t)(int64_t)((int)e - 50);
+            r.t = e % 41 == 40 ? 0xFFFFFFFFu : 0;  // a hole
+            r.aux = e;
+          }
+        }
+        on[0] = 0;
+        cpu::rolling_slide_rows(srecs.data(), scount.data(), s_nsrc, s_nsub, s_bcap, s_cap_log2,
+                                AGG_SUM_I64, sk.data(), sa.data(), sc.data(), so.data(), sr.data(),
+                                sflags.data(), ExprProg{}, ok.data(), ov.data(), ot.data(),
+                                oc.data(), on.data(), ocap, size, slide);
+        rows += on[0];
+        for (uint32_t i = 0; i < std::min(on[0], ocap); ++i)
+          if (oc[i] < 1 || oc[i] > size) return fail("sliding count window: element count");
+      }
+      uint64_t total = 0, want = 0;
+      for (size_t i = 0; i < s_slots; ++i) {
+        total += so[i];
+        want += so[i] / slide;
+      }
+      if (sflags[0] || !total || rows != want) return fail("sliding count window: row count");
+    }
   }
   uint64_t chk[kChkN] = {0, 0, 0, 0};
   cpu::check_table(keys_g.data(), nsub, nsub_log2, cap_log2, chk);

@@ -19,6 +19,8 @@ A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folde
 """
 from __future__ import annotations
 
+import math
+
 from ..ops import expr as E
 from ..runtime.executor import Transformation
 from . import windowing as W
@@ -436,10 +438,34 @@ def _count_window_size(ws) -> int | None:
     return inner.count
 
 
+SLIDE_MAX_PANES = 64  # csrc kSlideMaxPanes: panes of gcd(size, slide) elements per window
+
+
+def _count_window_slide(ws) -> tuple[int, int] | None:
+    """(size, slide) of a sliding count window: GlobalWindows + CountEvictor.of(size) (evicting
+    before the function) + a bare CountTrigger(slide) (KeyedStream.countWindow(size, slide)), with
+    at most SLIDE_MAX_PANES panes per window; None for anything else."""
+    ev, tr = ws._evictor, ws._trigger
+    if type(ev) is not W.CountEvictor or ev.after or type(tr) is not W.CountTrigger:
+        return None
+    size, slide = ev.max_count, tr.count
+    for x in (size, slide):
+        if not isinstance(x, int) or isinstance(x, bool) or not 1 <= x < (1 << 31):
+            return None
+    if size // math.gcd(size, slide) > SLIDE_MAX_PANES:
+        return None
+    return size, slide
+
+
 def _lower_count_window(env, t, ws, spec, meta, children) -> None:
     """keyBy(k).countWindow(n).sum/min/max(p) | reduce(field-wise sum) | aggregate(avg) ->
-    NativeCountWindowOp (segmented-scan count windows on the GPU / C++ twin)."""
-    n = _count_window_size(ws)
+    NativeCountWindowOp (segmented-scan count windows on the GPU / C++ twin); countWindow(size,
+    slide) with the same functions -> the same operator in its sliding mode."""
+    n, slide = _count_window_size(ws), 0
+    if n is None:
+        shape = _count_window_slide(ws)
+        if shape is not None:
+            n, slide = shape
     if n is None or ws.keyed is None or ws.keyed.key_pos is None or ws._late_tag is not None:
         return
     key_pos = ws.keyed.key_pos
@@ -491,9 +517,9 @@ def _lower_count_window(env, t, ws, spec, meta, children) -> None:
     key_fn = ws.keyed.key_fn
 
     def factory():
-        return NativeCountWindowOp(count=n, result_builder=builder, ok_arities=ok, key_fn=key_fn,
-                                   key_pos=key_pos, val_pos=val_pos, kind=kind, device=device,
-                                   fallback_factory=fallback)
+        return NativeCountWindowOp(count=n, slide=slide, result_builder=builder, ok_arities=ok,
+                                   key_fn=key_fn, key_pos=key_pos, val_pos=val_pos, kind=kind,
+                                   device=device, fallback_factory=fallback)
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)

@@ -166,6 +166,47 @@ def config2(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 10_000,
             "alerts": alerts, "keys": keys, "events_per_step": batch, "device": str(dev)}
 
 
+def config11(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 10_000,
+             size: int = 100, slide: int | None = None, device: str = "cuda") -> dict:
+    """Keyed count-window sum on the sort path, config 2's batch and key space: ``countWindow(size,
+    slide)`` (the pane scan), or without `slide` the tumbling ``countWindow(size)`` on the same
+    data (the segmented scan it is measured against). The fired rows stay on the device (the
+    sliding window of slide 1 fires on every element); their count is read once at the end."""
+    dev = torch.device(device)
+    op = KeyedRollingOperator(agg=K.AGG_SUM_I64, device=dev, max_keys=keys, batch_capacity=batch,
+                              count_window=size, count_slide=slide or 0)
+    op.sort_free = False
+    kt = torch.empty(batch, dtype=torch.int64, device=dev)
+    tt = torch.empty_like(kt)
+    vt = torch.empty_like(kt)
+    step_i = [0]
+    fired = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def step():
+        K.gen_events(kt, tt, vt, seed=2, stream_id=0, idx0=step_i[0] * batch, nkeys=keys,
+                     ts_base=0, ts_span=1000, disorder=0, val_lo=0, val_span=100)
+        fired.add_(op.process(kt, vt, to_host=False))
+        step_i[0] += 1
+
+    for _ in range(warmup):
+        step()
+    fired.zero_()
+    _sync(dev)
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    _sync(dev)
+    dt = time.perf_counter() - t0
+    op.check()
+    pane = math.gcd(size, slide) if slide else size
+    return {"config": 11, "window": "sliding" if slide else "tumbling", "size": size,
+            "slide": slide or size, "pane": pane, "panes_per_window": size // pane,
+            "metric": f"events/sec (keyed count-window sum, {keys // 1000}k keys, radix-sort path)",
+            "value": batch * steps / dt, "unit": "events/s", "ms_per_step": dt / steps * 1e3,
+            "rows": int(fired.item()), "keys": keys, "events_per_step": batch,
+            "device": str(dev)}
+
+
 def config2_spill(steps: int, warmup: int, batch: int = 1 << 22, active: int = 500_000,
                   drift: int = 50_000, table_keys: int = 1_000_000, revisit: float = 0.01,
                   device: str = "cuda") -> dict:
@@ -1009,7 +1050,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1038,6 +1079,9 @@ def main(argv=None) -> int:
     ap.add_argument("--sort-path", action="store_true",
                     help="config 2: the radix-sort rolling path instead of the sort-free one")
     ap.add_argument("--keys", type=int, default=None, help="config 2: key space (default 10k)")
+    ap.add_argument("--size", type=int, default=100, help="config 11: count-window size")
+    ap.add_argument("--slide", type=int, default=None,
+                    help="config 11: count-window slide (omitted: the tumbling countWindow(size))")
     ap.add_argument("--latency-fire", type=int, default=0,
                     help="config 4: fire right away when at most this many windows are due "
                          "(latency-bounded mode; 0 = pipelined firing)")
@@ -1078,6 +1122,9 @@ def main(argv=None) -> int:
     elif a.config == 10:
         r = config10(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 1_000_000,
                      device=a.device, top_n=a.top_n)
+    elif a.config == 11:
+        r = config11(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 10_000, size=a.size,
+                     slide=a.slide, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

@@ -1207,13 +1207,22 @@ class NativeCountWindowOp(NativeRollingOp):
     chapter3/README.md:4) on the native ``KeyedRollingOperator`` in count-window mode: the
     segmented wave scan emits one row per completed window, in input order of the completing
     elements, with the GlobalWindow's timestamp (Long.MAX_VALUE). Only lowered when the fields
-    other than key and value are dead downstream (planner), like the time windows."""
+    other than key and value are dead downstream (planner), like the time windows.
+
+    ``countWindow(n, slide)`` (GlobalWindows + CountEvictor(n) + CountTrigger(slide)) is the same
+    operator with ``slide`` set: the engine's pane scan fires at every slide-th element of a key
+    over its last min(ordinal, n) elements and returns that element count with every row."""
 
     name = "Window(native count)"
 
-    def __init__(self, *, count: int, result_builder, ok_arities=None, **kw):
+    def __init__(self, *, count: int, result_builder, ok_arities=None, slide: int = 0, **kw):
+        """slide > 0: sliding count windows ``countWindow(count, slide)`` (GlobalWindows +
+        CountEvictor(count) + CountTrigger(slide)): a row at every slide-th element of a key over
+        its last min(ordinal, count) elements; avg and count read that size from the engine's
+        count column."""
         super().__init__(**kw)
         self.count = int(count)
+        self.slide = int(slide)
         self.result_builder = result_builder
         self.ok_arities = ok_arities
 
@@ -1230,7 +1239,8 @@ class NativeCountWindowOp(NativeRollingOp):
                ("avg", False): K.AGG_AVG_I64, ("avg", True): K.AGG_AVG_F64}[(self.kind, self.is_float)]
         self.op = KeyedRollingOperator(agg=agg, device=torch.device(self.device),
                                        max_keys=self.max_keys, parallelism=1,
-                                       batch_capacity=1024, count_window=self.count)
+                                       batch_capacity=1024, count_window=self.count,
+                                       count_slide=self.slide)
         return True
 
     def _result(self, raw: int):
@@ -1240,6 +1250,31 @@ class NativeCountWindowOp(NativeRollingOp):
             s = float(np.int64(raw).view(np.float64)) if self.is_float else float(raw)
             return s / self.count
         return super()._result(raw)
+
+    def _device_ok(self, batches: list) -> bool:
+        # sliding mode: rows are rebuilt on the host from the engine's (value, count) columns
+        return not self.slide and super()._device_ok(batches)
+
+    def _rows_out(self, rows, ts_of) -> list:
+        if rows.counts is None or self.kind != "avg":
+            return super()._rows_out(rows, ts_of)
+        # Sliding mode: the early windows of a key hold fewer than `count` elements, so the
+        # average divides by each row's own element count.
+        from ..utils.hashing import flink_murmur
+
+        order = np.argsort(rows.tags & 0xFFFFFFFF, kind="stable")  # back to input order
+        P, MP = self.ctx.parallelism, self.ctx.max_parallelism
+        raws = rows.values[order]
+        sums = raws.view(np.float64) if self.is_float else raws.astype(np.float64)
+        subs: dict = {}
+        out = []
+        for k, sm, c in zip(rows.keys[order].tolist(), sums.tolist(), rows.counts[order].tolist()):
+            sub = subs.get(k)
+            if sub is None:
+                key_obj = self.dict.get(k) if self.str_keys else k
+                sub = subs[k] = (flink_murmur(java_hash(key_obj)) % MP) * P // MP
+            out.append(Rec(self._value(k, sm / c), LONG_MAX, sub))
+        return out
 
     def _value(self, k: int, res):
         key_obj = self.dict.get(k) if self.str_keys else k

@@ -7,6 +7,10 @@ rolling pass. GPU: rolling_lookup (HBM hash table insert/find, 64-bit sort keys
 slot|src|arrival) -> one radix sort -> rolling_heads -> rolling_scan (one wave per key,
 ordered shuffle scan seeded by the stored state, fused filter, compacted rows). CPU: the
 sequential twin ``rolling_rows``. Output rows are in per-key arrival order.
+
+Count windows run on the same passes: tumbling ``countWindow(n)`` as a segmented rolling_scan,
+sliding ``countWindow(n, s)`` as rolling_slide_scan over panes of gcd(n, s) elements (CPU twin
+``rolling_slide_rows``), see docs/DESIGN.md §15.
 """
 from __future__ import annotations
 
@@ -24,6 +28,9 @@ from ..parallel.comm import Comm, LocalComm
 I64_MIN, I64_MAX = K.I64_MIN, K.I64_MAX
 
 
+SLIDE_MAX_PANES = 64  # csrc kSlideMaxPanes: one pane partial per lane of a wave
+
+
 def _next_pow2(x: int) -> int:
     return 1 << max(0, int(x - 1).bit_length())
 
@@ -33,6 +40,7 @@ class RollingRows:
     keys: np.ndarray   # uint64
     values: np.ndarray  # int64 raw (f64 bit pattern for float aggregates; count for COUNT)
     tags: np.ndarray   # int64: src rank << 32 | index in that rank's batch
+    counts: np.ndarray | None = None  # uint32 elements per window (sliding count windows only)
 
 
 class KeyedRollingOperator:
@@ -41,12 +49,19 @@ class KeyedRollingOperator:
                  max_parallelism: int = 128, batch_capacity: int = 1 << 20,
                  cap_log2: int | None = None, filter_prog: E.Program = E.EMPTY, emit_capacity: int | None = None,
                  count_window: int = 0, dense_keys: bool = False, spill: bool = False,
-                 spill_load: float = 0.75, spill_target: float = 0.5):
+                 spill_load: float = 0.75, spill_target: float = 0.5, count_slide: int = 0):
         """count_window = n > 0: tumbling count windows instead of a rolling aggregate
         (``keyBy(..).countWindow(n)`` with an incremental reduce/aggregate: GlobalWindows +
         PurgingTrigger(CountTrigger(n)), chapter2/README.md:78) -- a row is emitted when a key's
         open window reaches n elements (value = the window's aggregate; for avg the sum, the
         count is n), and the state keeps each key's open window.
+
+        count_slide = s > 0 (with count_window = n): sliding count windows ``countWindow(n, s)``
+        (GlobalWindows + CountEvictor(n) + CountTrigger(s)) -- a row at every s-th element of a
+        key over its last min(ordinal, n) elements; RollingRows.counts carries that element
+        count. State: panes of gcd(n, s) elements -- the open pane in (acc, cnt), the last
+        n / gcd(n, s) <= 64 completed panes in ``ring_g`` (slot-major), the key's 64-bit element
+        ordinal in ``ord_g``. Hashed keys on the sort path only (no dense ids, no spill tier).
 
         dense_keys: keys are dictionary ids in [0, max_keys) (columnar ingest, device-generated
         ids): the slot IS the key id -- no hash probe. Single-rank GPU sort-free COUNT only.
@@ -67,6 +82,20 @@ class KeyedRollingOperator:
             raise ValueError("count window size out of range")
         if agg in (K.AGG_AVG_F64, K.AGG_AVG_I64) and not self.count_window:
             raise ValueError("rolling avg is not a Flink rolling aggregate")
+        self.count_slide = int(count_slide)
+        self.ppw = 0
+        if self.count_slide:
+            if self.count_slide < 0 or self.count_slide >= (1 << 31):
+                raise ValueError("count window slide out of range")
+            if not self.count_window:
+                raise ValueError("count_slide needs count_window (the window size)")
+            if spill or dense_keys:
+                raise ValueError("sliding count windows: hashed HBM state only "
+                                 "(no spill tier, no dense ids)")
+            self.ppw = self.count_window // math.gcd(self.count_window, self.count_slide)
+            if self.ppw > SLIDE_MAX_PANES:
+                raise ValueError(f"sliding count windows: {self.ppw} panes per window "
+                                 f"(size / gcd(size, slide)), at most {SLIDE_MAX_PANES}")
         self.parallelism = parallelism or self.world
         self.max_parallelism = max_parallelism
         self.filter_prog = filter_prog
@@ -92,6 +121,9 @@ class KeyedRollingOperator:
         self.acc_g = torch.zeros(self.nslots, dtype=torch.int64, device=dev)
         self.cnt_g = torch.zeros(self.nslots, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(4, dtype=torch.int32, device=dev)
+        if self.count_slide:
+            self.ord_g = torch.zeros(self.nslots, dtype=torch.int64, device=dev)
+            self.ring_g = torch.zeros(self.nslots * self.ppw, dtype=torch.int64, device=dev)
         self.spill = bool(spill)
         if self.spill:
             if self.dense:
@@ -124,7 +156,8 @@ class KeyedRollingOperator:
         self.direct_single_rank = True  # world 1 on the GPU: no partition pass (_process_direct)
         # Sort-free COUNT path (rolling_hist) when the table fits its LDS counter; False forces
         # the sort path (A/B, tests).
-        self.sort_free = not self.spill  # the spill tier tracks slots through the sort path
+        # (the spill tier tracks slots through the sort path; sliding count windows scan panes)
+        self.sort_free = not self.spill and not self.count_slide
         self._hist_tmp = None
         if self.dense:
             code, consts = filter_prog.as_args()
@@ -158,6 +191,8 @@ class KeyedRollingOperator:
         self.out_key = torch.empty(ocap, dtype=torch.int64, device=dev)
         self.out_val = torch.empty(ocap, dtype=torch.int64, device=dev)
         self.out_tag = torch.empty(ocap, dtype=torch.int64, device=dev)
+        self.out_cnt = (torch.empty(ocap, dtype=torch.int32, device=dev)
+                        if self.count_slide else None)
         # flags[2] is the emitted-row cursor: one D2H returns the row count with the table-full
         # (bit0) and reserved-key (bit2) flags of flags[0].
         self.out_n = self.flags[2:3]
@@ -214,6 +249,9 @@ class KeyedRollingOperator:
         n_in = self.n_buf[0:1]
         m.gpu_rolling_heads(sk.data_ptr(), n_in.data_ptr(), n, self.heads.data_ptr(),
                             self.n_buf[1:2].data_ptr(), shift, st)
+        if self.count_slide:
+            self._slide_scan(m, sk, n_in, min(n, self.nslots), code, consts, cap, shift, shift, st)
+            return self._emit(to_host)
         m.gpu_rolling_scan(self.agg, sk.data_ptr(), 0, self.vals_out.data_ptr(), n_in.data_ptr(),
                            self.heads.data_ptr(), self.n_buf[1:2].data_ptr(),
                            min(n, self.nslots), self.acc_g.data_ptr(), self.cnt_g.data_ptr(),
@@ -221,6 +259,18 @@ class KeyedRollingOperator:
                            self.out_val.data_ptr(), self.out_tag.data_ptr(),
                            self.out_n.data_ptr(), cap, shift, shift, st, self.count_window)
         return self._emit(to_host)
+
+    def _slide_scan(self, m, sk, n_in, max_segments, code, consts, cap, abits, shift, st):
+        """The sliding count-window scan over the sorted batch (rolling_slide_scan_kernel)."""
+        m.gpu_rolling_slide_scan(self.agg, sk.data_ptr(), self.vals_out.data_ptr(),
+                                 n_in.data_ptr(), self.heads.data_ptr(),
+                                 self.n_buf[1:2].data_ptr(), max_segments, self.acc_g.data_ptr(),
+                                 self.cnt_g.data_ptr(), self.ord_g.data_ptr(),
+                                 self.ring_g.data_ptr(), self.keys_g.data_ptr(), code, consts,
+                                 self.out_key.data_ptr(), self.out_val.data_ptr(),
+                                 self.out_tag.data_ptr(), self.out_cnt.data_ptr(),
+                                 self.out_n.data_ptr(), cap, abits, shift, st, self.count_window,
+                                 self.count_slide)
 
     def process(self, keys: torch.Tensor, vals: torch.Tensor, to_host: bool = True):
         """Update state with one micro-batch; returns the emitted rows (host) or the device count."""
@@ -299,6 +349,10 @@ class KeyedRollingOperator:
                 n_in = self.n_buf[0:1]
                 m.gpu_rolling_heads(sk.data_ptr(), n_in.data_ptr(), total,
                                     self.heads.data_ptr(), self.n_buf[1:2].data_ptr(), shift, st)
+                if self.count_slide:
+                    self._slide_scan(m, sk, n_in, min(total, self.nslots), code, consts, cap,
+                                     abits, shift, st)
+                    return self._emit(to_host)
                 m.gpu_rolling_scan(self.agg, sk.data_ptr(), 0,
                                    self.vals_out.data_ptr(), n_in.data_ptr(), self.heads.data_ptr(),
                                    self.n_buf[1:2].data_ptr(), min(total, self.nslots),
@@ -307,6 +361,16 @@ class KeyedRollingOperator:
                                    self.out_val.data_ptr(), self.out_tag.data_ptr(),
                                    self.out_n.data_ptr(), cap, abits, shift, st,
                                    self.count_window)
+        elif self.count_slide:
+            m.cpu_rolling_slide_rows(self.recv.data_ptr(), self.recv_counts.data_ptr(), self.world,
+                                     self.nsub, self.bucket_cap, self.cap_log2, self.agg,
+                                     self.keys_g.data_ptr(), self.acc_g.data_ptr(),
+                                     self.cnt_g.data_ptr(), self.ord_g.data_ptr(),
+                                     self.ring_g.data_ptr(), self.flags.data_ptr(), code, consts,
+                                     self.out_key.data_ptr(), self.out_val.data_ptr(),
+                                     self.out_tag.data_ptr(), self.out_cnt.data_ptr(),
+                                     self.out_n.data_ptr(), cap, self.count_window,
+                                     self.count_slide)
         else:
             m.cpu_rolling_rows(self.recv.data_ptr(), self.recv_counts.data_ptr(), self.world,
                                self.nsub, self.bucket_cap, self.cap_log2, self.agg,
@@ -437,7 +501,9 @@ class KeyedRollingOperator:
     def _emit(self, to_host: bool):
         if not to_host:
             return self.out_n
-        if self.device.type == "cuda" and self.out_key.numel() % 2 == 0:
+        # (the slab copy moves 16-byte granules: the uint32 count column needs 4 rows each)
+        if self.device.type == "cuda" and \
+                self.out_key.numel() % (4 if self.count_slide else 2) == 0:
             # One device-counted copy of the emitted rows and the sticky flags into a pinned slab
             # (the copy kernel reads the row count itself) and ONE wait -- instead of a flag read
             # plus three pageable D2H copies, each its own sync. The rows are copied out of the
@@ -446,17 +512,22 @@ class KeyedRollingOperator:
 
             if getattr(self, "_emit_pool", None) is None:
                 self._emit_pool = PinnedSlabPool(max_slabs=4)
-            hr = CountedHostRows(self._emit_pool, [self.out_key, self.out_val, self.out_tag],
-                                 self.out_n, [self.flags])
+            outs = [self.out_key, self.out_val, self.out_tag]
+            if self.count_slide:
+                outs.append(self.out_cnt)
+            hr = CountedHostRows(self._emit_pool, outs, self.out_n, [self.flags])
             hr.wait()
             self._check_flags(hr.fixed(0).tolist())
             k = min(int(hr.fixed(0)[2]), self.out_key.numel())
             cols = hr.columns(k)
-            return RollingRows(cols[0].copy().view(np.uint64), cols[1].copy(), cols[2].copy())
+            return RollingRows(cols[0].copy().view(np.uint64), cols[1].copy(), cols[2].copy(),
+                               cols[3].copy().view(np.uint32) if self.count_slide else None)
         k = min(self.check(), self.out_key.numel())
         return RollingRows(self.out_key[:k].cpu().numpy().copy().view(np.uint64),
                            self.out_val[:k].cpu().numpy().copy(),
-                           self.out_tag[:k].cpu().numpy().copy())
+                           self.out_tag[:k].cpu().numpy().copy(),
+                           self.out_cnt[:k].cpu().numpy().copy().view(np.uint32)
+                           if self.count_slide else None)
 
     def _dummy_ts(self, n: int) -> torch.Tensor:
         t = getattr(self, "_ts0", None)
@@ -497,15 +568,26 @@ class KeyedRollingOperator:
         kg = K.keygroups(keys, max_parallelism=self.max_parallelism).cpu().numpy()
         meta = {"kind": "rolling", "agg": self.agg, "records_in": self.records_in,
                 "steps": self.steps, "count_window": self.count_window}
+        if self.count_slide:
+            # the ordinal and the pane ring, one column per ring position (pane p at p % ppw)
+            meta["count_slide"] = self.count_slide
+            cols["ord"] = self.ord_g[live].cpu().numpy()
+            ring = self.ring_g.view(self.nslots, self.ppw)[live].cpu().numpy()
+            for j in range(self.ppw):
+                cols[f"ring{j}"] = np.ascontiguousarray(ring[:, j])
         return OperatorSnapshot(kg, cols, meta)
 
     def restore_state(self, rows: dict, meta: dict) -> None:
-        if meta["agg"] != self.agg or meta.get("count_window", 0) != self.count_window:
+        if meta["agg"] != self.agg or meta.get("count_window", 0) != self.count_window \
+                or meta.get("count_slide", 0) != self.count_slide:
             raise ValueError("checkpoint aggregate / count window does not match the operator")
         self.records_in, self.steps = meta["records_in"], meta["steps"]
         self.keys_g.fill_(-1)
         self.acc_g.zero_()
         self.cnt_g.zero_()
+        if self.count_slide:
+            self.ord_g.zero_()
+            self.ring_g.zero_()
         if not len(rows["key"]):
             return
         if self.spill:
@@ -533,6 +615,11 @@ class KeyedRollingOperator:
             raise RuntimeError("restore: keyed state does not fit the table (raise max_keys)")
         self.acc_g[slots] = torch.from_numpy(np.ascontiguousarray(rows["acc"])).to(dev)
         self.cnt_g[slots] = torch.from_numpy(np.ascontiguousarray(rows["cnt"])).to(dev)
+        if self.count_slide:
+            self.ord_g[slots] = torch.from_numpy(np.ascontiguousarray(rows["ord"])).to(dev)
+            ring = np.stack([rows[f"ring{j}"] for j in range(self.ppw)], axis=1)
+            self.ring_g.view(self.nslots, self.ppw)[slots] = \
+                torch.from_numpy(np.ascontiguousarray(ring)).to(dev)
 
 
 class RollingSpillStore:
