@@ -566,6 +566,19 @@ PYBIND11_MODULE(_mxs_native, m) {
                       P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot), P<uint32_t>(on), out_cap,
                       abits, shift, stream, count_n);
   });
+  m.def("gpu_rolling_argscan", [](int agg, intptr_t sk, intptr_t vals, intptr_t n_in,
+                                  intptr_t heads, intptr_t n_heads, int64_t max_segments,
+                                  intptr_t acc_g, intptr_t cnt_g, intptr_t keys_g, intptr_t ok,
+                                  intptr_t ov, intptr_t ot, intptr_t os, intptr_t on,
+                                  uint32_t out_cap, intptr_t wk, intptr_t ws, int abits, int shift,
+                                  intptr_t stream, uint32_t count_n) {
+    gpu::rolling_argscan(agg, P<int64_t>(sk), P<uint64_t>(vals), P<uint32_t>(n_in),
+                         P<uint32_t>(heads), P<uint32_t>(n_heads), max_segments,
+                         P<uint64_t>(acc_g), P<uint32_t>(cnt_g), P<uint64_t>(keys_g),
+                         P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot), P<int64_t>(os),
+                         P<uint32_t>(on), out_cap, P<uint64_t>(wk), P<int64_t>(ws), abits, shift,
+                         stream, count_n);
+  });
   m.def("gpu_rolling_slide_scan", [](int agg, intptr_t sk, intptr_t vals, intptr_t n_in,
                                      intptr_t heads, intptr_t n_heads, int64_t max_segments,
                                      intptr_t acc_g, intptr_t cnt_g, intptr_t ord_g,
@@ -1285,6 +1298,19 @@ PYBIND11_MODULE(_mxs_native, m) {
                       P<uint64_t>(keys_g), P<uint64_t>(acc_g), P<uint32_t>(cnt_g),
                       P<uint32_t>(flags), f, P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot),
                       P<uint32_t>(on), out_cap, count_n);
+  });
+  m.def("cpu_rolling_arg_rows", [](intptr_t recs, intptr_t counts, int nsrc, int nsub,
+                                   uint32_t bcap, int cap_log2, int agg, intptr_t keys_g,
+                                   intptr_t acc_g, intptr_t cnt_g, intptr_t flags, intptr_t ok,
+                                   intptr_t ov, intptr_t ot, intptr_t os, intptr_t on,
+                                   uint32_t out_cap, intptr_t wk, intptr_t ws, intptr_t wn,
+                                   uint32_t count_n) {
+    py::gil_scoped_release nogil;
+    cpu::rolling_arg_rows(P<Rec>(recs), P<uint32_t>(counts), nsrc, nsub, bcap, cap_log2, agg,
+                          P<uint64_t>(keys_g), P<uint64_t>(acc_g), P<uint32_t>(cnt_g),
+                          P<uint32_t>(flags), P<uint64_t>(ok), P<uint64_t>(ov), P<int64_t>(ot),
+                          P<int64_t>(os), P<uint32_t>(on), out_cap, P<uint64_t>(wk),
+                          P<int64_t>(ws), P<uint32_t>(wn), count_n);
   });
   m.def("cpu_rolling_slide_rows", [](intptr_t recs, intptr_t counts, int nsrc, int nsub,
                                      uint32_t bcap, int cap_log2, int agg, intptr_t keys_g,

@@ -10,6 +10,7 @@
 #include <numeric>
 #include <stdexcept>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "mxs_kernels.h"
@@ -399,6 +400,80 @@ void rolling_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub, u
     }
   }
   *out_n = n;
+}
+
+// maxBy / minBy: the rolling fold over (value, winner), the definition of gpu::rolling_argscan's
+// result. A later record replaces the winner only if it is strictly better (signed compare for
+// I64, IEEE compare for F64), so ties keep the earlier record. out_src is the winner's tag
+// (src << 32 | arrival), -1 for the record already held in state. Every key touched by the batch
+// gets one (win_key, win_src) pair: the winner of its state after the batch (-1 the stored
+// record, -2 count windows with an empty open window).
+static bool arg_better(int agg, uint64_t later, uint64_t earlier) {
+  switch (agg) {
+    case AGG_MAX_I64: return (int64_t)later > (int64_t)earlier;
+    case AGG_MIN_I64: return (int64_t)later < (int64_t)earlier;
+    case AGG_MAX_F64: return as_f64(later) > as_f64(earlier);
+    default: return as_f64(later) < as_f64(earlier);
+  }
+}
+
+void rolling_arg_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub,
+                      uint32_t bucket_cap, int cap_log2, int agg, uint64_t* keys_g, uint64_t* acc_g,
+                      uint32_t* cnt_g, uint32_t* flags, uint64_t* out_key, uint64_t* out_val,
+                      int64_t* out_tag, int64_t* out_src, uint32_t* out_n, uint32_t out_cap,
+                      uint64_t* win_key, int64_t* win_src, uint32_t* win_n, uint32_t count_n) {
+  if (agg != AGG_MAX_I64 && agg != AGG_MIN_I64 && agg != AGG_MAX_F64 && agg != AGG_MIN_F64)
+    throw std::invalid_argument("rolling_arg_rows: min / max aggregates only");
+  const uint32_t mask = (1u << cap_log2) - 1;
+  uint32_t n = *out_n, nw = 0;
+  std::unordered_map<size_t, uint32_t> touched;  // slot -> index of its (win_key, win_src) pair
+  for (int sub = 0; sub < nsub; ++sub) {
+    uint64_t* keys = keys_g + ((size_t)sub << cap_log2);
+    bool inserted = false;
+    for (int src = 0; src < nsrc; ++src) {
+      const uint32_t c = std::min(counts[(size_t)src * nsub + sub], bucket_cap);
+      const Rec* seg = recs + ((size_t)src * nsub + sub) * bucket_cap;
+      for (uint32_t e = 0; e < c; ++e) {
+        const Rec& r = seg[e];
+        if (r.t == 0xFFFFFFFFu) continue;
+        const uint32_t s = probe_insert(keys, r.key, mask, &inserted);
+        if (s == kNoSlot) {
+          flags[0] |= 1u;
+          continue;
+        }
+        const size_t gi = ((size_t)sub << cap_log2) + s;
+        auto it = touched.find(gi);
+        if (it == touched.end()) {
+          it = touched.emplace(gi, nw).first;
+          win_key[nw] = r.key;
+          win_src[nw] = cnt_g[gi] ? -1 : -2;
+          ++nw;
+        }
+        int64_t& win = win_src[it->second];
+        const int64_t tag = ((int64_t)src << 32) | r.aux;
+        if (!cnt_g[gi] || arg_better(agg, r.val, acc_g[gi])) {
+          acc_g[gi] = r.val;
+          win = tag;
+        }
+        cnt_g[gi] += 1;
+        if (!count_n || cnt_g[gi] == count_n) {
+          if (n < out_cap) {
+            out_key[n] = r.key;
+            out_val[n] = acc_g[gi];
+            out_tag[n] = tag;
+            out_src[n] = win;
+          }
+          ++n;
+        }
+        if (count_n && cnt_g[gi] == count_n) {  // window purged: the next one starts empty
+          cnt_g[gi] = 0;
+          win = -2;
+        }
+      }
+    }
+  }
+  *out_n = n;
+  *win_n = nw;
 }
 
 // Sliding count windows countWindow(size, slide), the oracle of gpu::rolling_slide_scan. Per key:

@@ -3201,6 +3201,114 @@ __global__ __launch_bounds__(256) void rolling_scan_kernel(
   }
 }
 
+// Arg-select scan (maxBy / minBy): rolling_scan_kernel's walk over the pair (value word, winner).
+// The winner is the tag (src << 32 | arrival, the out_tag encoding) of the record that holds the
+// extremum; -1 is the record already held in state (the stored accumulator, or the leader of a
+// count window left open by an earlier batch). A later element replaces the winner only if it is
+// STRICTLY better (signed compare for I64, IEEE compare for F64: -0.0 ties 0.0), so ties keep
+// the earlier record -- Flink's maxBy(pos, first = true). roll_combine takes the later word on a
+// tie, which is harmless for a value and wrong for an argument: not used here.
+// Per head h the kernel also writes (win_key[h], win_src[h]): the key and the winner of its state
+// after the batch (-1: the stored record still wins; -2: count windows, the open window is empty).
+// No filter VM, no LDS.
+template <int AGG>
+__device__ __forceinline__ bool arg_better(uint64_t later, uint64_t earlier) {
+  if (AGG == AGG_MAX_I64) return (int64_t)later > (int64_t)earlier;
+  if (AGG == AGG_MIN_I64) return (int64_t)later < (int64_t)earlier;
+  if (AGG == AGG_MAX_F64) return as_f64(later) > as_f64(earlier);
+  return as_f64(later) < as_f64(earlier);
+}
+
+template <int AGG>
+__global__ __launch_bounds__(256) void rolling_argscan_kernel(
+    const int64_t* __restrict__ sk, const uint64_t* __restrict__ vals,
+    const uint32_t* __restrict__ n_in, const uint32_t* __restrict__ heads,
+    const uint32_t* __restrict__ n_heads, uint64_t* __restrict__ acc_g,
+    uint32_t* __restrict__ cnt_g, const uint64_t* __restrict__ keys_g,
+    uint64_t* __restrict__ out_key, uint64_t* __restrict__ out_val, int64_t* __restrict__ out_tag,
+    int64_t* __restrict__ out_src, uint32_t* __restrict__ out_n, uint32_t out_cap,
+    uint64_t* __restrict__ win_key, int64_t* __restrict__ win_src, int abits, int shift,
+    uint32_t count_n) {
+  const uint32_t n = *n_in, nh = *n_heads;
+  const int lane = lane_id();
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  const int64_t amask = ((int64_t)1 << abits) - 1, smask = ((int64_t)1 << (shift - abits)) - 1;
+  for (uint32_t h = wave; h < nh; h += nwaves) {  // wave-uniform loop
+    const uint32_t start = heads[h];
+    const uint64_t slot = (uint64_t)(sk[start] >> shift);
+    uint32_t end = start + 1;
+    for (;;) {  // segment end, as in rolling_scan_kernel
+      const uint32_t i = end + lane;
+      const bool same = i < n && (uint64_t)(sk[i] >> shift) == slot && sk[i] != INT64_MAX;
+      const unsigned long long m = __ballot(!same);
+      if (m) {
+        end += (uint32_t)__ffsll((long long)m) - 1;
+        break;
+      }
+      end += 64;
+    }
+    const uint32_t c0 = cnt_g[slot];
+    uint64_t carry = c0 ? acc_g[slot] : 0;
+    int64_t carry_w = -1;  // the stored record
+    bool have = c0 != 0;
+    const uint64_t key = keys_g[slot];
+    uint32_t cnt = c0;
+    for (uint32_t b0 = start; b0 < end; b0 += 64) {
+      const uint32_t i = b0 + lane;
+      const bool in = i < end;
+      uint64_t v = in ? vals[i] : 0;
+      const int64_t k = in ? sk[i] : 0;
+      const int64_t tag = (((k >> abits) & smask) << 32) | (k & amask);  // src << 32 | arrival
+      int64_t w = tag;
+      // Inclusive segmented wave scan of (value, winner); y is the earlier partial.
+      int f = count_n && (cnt + (uint32_t)lane) % count_n == 0;
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t y = __shfl_up(v, o);
+        const int64_t yw = __shfl_up(w, o);
+        const int g = __shfl_up(f, o);
+        if (lane >= o && in && !f) {
+          if (!arg_better<AGG>(v, y)) {
+            v = y;
+            w = yw;
+          }
+          f = g;
+        }
+      }
+      if (have && !f && !arg_better<AGG>(v, carry)) {
+        v = carry;
+        w = carry_w;
+      }
+      const uint32_t nin = (end - b0) < 64 ? (end - b0) : 64;
+      const bool emit = in && (!count_n || (cnt + (uint32_t)lane + 1) % count_n == 0);
+      const unsigned long long m = __ballot(emit);
+      uint32_t wb = 0;
+      if (lane == 0 && m) wb = atomicAdd(out_n, (uint32_t)__popcll(m));
+      wb = __shfl(wb, 0);
+      if (emit) {
+        const uint32_t q = wb + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (q < out_cap) {
+          out_key[q] = key;
+          out_val[q] = v;
+          out_tag[q] = tag;
+          out_src[q] = w;
+        }
+      }
+      carry = __shfl(v, (int)nin - 1);
+      carry_w = __shfl(w, (int)nin - 1);
+      have = true;
+      cnt += nin;
+    }
+    if (lane == 0) {
+      acc_g[slot] = carry;
+      const uint32_t left = count_n ? cnt % count_n : cnt;
+      cnt_g[slot] = left;
+      win_key[h] = key;
+      win_src[h] = count_n && left == 0 ? -2 : carry_w;
+    }
+  }
+}
+
 // Sliding count windows (countWindow(size, slide): GlobalWindows + CountEvictor(size) +
 // CountTrigger(slide)) over panes of ordinals: pane = gcd(size, slide) elements, ppw = size / pane
 // panes per window (<= 64). Per slot: acc_g/cnt_g hold the open pane, ord_g the key's 64-bit
@@ -6152,6 +6260,24 @@ void rolling_scan(int agg, const int64_t* sk, const int64_t* perm, const uint64_
     MXS_R(AGG_AVG_I64) MXS_R(AGG_AVG_F64)
 #undef MXS_R
     default: throw std::runtime_error("rolling_scan: unsupported aggregate");
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void rolling_argscan(int agg, const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
+                     const uint32_t* heads, const uint32_t* n_heads, int64_t max_segments,
+                     uint64_t* acc_g, uint32_t* cnt_g, const uint64_t* keys_g, uint64_t* out_key,
+                     uint64_t* out_val, int64_t* out_tag, int64_t* out_src, uint32_t* out_n,
+                     uint32_t out_cap, uint64_t* win_key, int64_t* win_src, int abits, int shift,
+                     intptr_t stream, uint32_t count_n) {
+  check_roll_layout(abits, shift);
+  const int grid = grid_for(max_segments * 64, 256, 4096);
+  hipStream_t s = (hipStream_t)stream;
+  switch (agg) {
+#define MXS_R(A) case A: hipLaunchKernelGGL(rolling_argscan_kernel<A>, dim3(grid), dim3(256), 0, s, sk, vals, n_in, heads, n_heads, acc_g, cnt_g, keys_g, out_key, out_val, out_tag, out_src, out_n, out_cap, win_key, win_src, abits, shift, count_n); break;
+    MXS_R(AGG_MIN_I64) MXS_R(AGG_MAX_I64) MXS_R(AGG_MIN_F64) MXS_R(AGG_MAX_F64)
+#undef MXS_R
+    default: throw std::invalid_argument("rolling_argscan: min / max aggregates only");
   }
   HIP_CHECK(hipGetLastError());
 }

@@ -446,6 +446,17 @@ void rolling_scan(int agg, const int64_t* sk, const int64_t* perm, const uint64_
                   const ExprProg& filt, uint64_t* out_key, uint64_t* out_val, int64_t* out_tag,
                   uint32_t* out_n, uint32_t out_cap, int abits, int shift, intptr_t stream,
                   uint32_t count_n = 0);
+// Arg-select scan (maxBy / minBy; the four MIN / MAX aggregates): rolling_scan over the pair
+// (value word, winner). out_src[q] is the winning record's tag (src << 32 | arrival), -1 when the
+// winner is the record already held in state; ties keep the earlier record. Per head h:
+// win_key[h] and win_src[h], the winner of the key's state after the batch (-1 stored record,
+// -2 count windows: the open window is empty).
+void rolling_argscan(int agg, const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
+                     const uint32_t* heads, const uint32_t* n_heads, int64_t max_segments,
+                     uint64_t* acc_g, uint32_t* cnt_g, const uint64_t* keys_g, uint64_t* out_key,
+                     uint64_t* out_val, int64_t* out_tag, int64_t* out_src, uint32_t* out_n,
+                     uint32_t out_cap, uint64_t* win_key, int64_t* win_src, int abits, int shift,
+                     intptr_t stream, uint32_t count_n = 0);
 // Sliding count windows countWindow(size, slide) over the same sorted batch: pane = gcd(size,
 // slide) elements, ppw = size / pane <= kSlideMaxPanes panes per window. ord_g[nslots] is each
 // key's element ordinal, ring_g[nslots * ppw] the completed pane partials (pane p of a slot at
@@ -576,6 +587,14 @@ void rolling_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub, u
                   int cap_log2, int agg, uint64_t* keys_g, uint64_t* acc_g, uint32_t* cnt_g,
                   uint32_t* flags, const ExprProg& filt, uint64_t* out_key, uint64_t* out_val,
                   int64_t* out_tag, uint32_t* out_n, uint32_t out_cap, uint32_t count_n = 0);
+// The twin of gpu::rolling_argscan and the definition of its result: a plain left fold per key in
+// (src, arrival) order with the strict compare. One (win_key, win_src) pair per key touched by
+// the batch, in first-touch order; *win_n is their number.
+void rolling_arg_rows(const Rec* recs, const uint32_t* counts, int nsrc, int nsub,
+                      uint32_t bucket_cap, int cap_log2, int agg, uint64_t* keys_g, uint64_t* acc_g,
+                      uint32_t* cnt_g, uint32_t* flags, uint64_t* out_key, uint64_t* out_val,
+                      int64_t* out_tag, int64_t* out_src, uint32_t* out_n, uint32_t out_cap,
+                      uint64_t* win_key, int64_t* win_src, uint32_t* win_n, uint32_t count_n = 0);
 // The sliding count-window twin of gpu::rolling_slide_scan (same state layout, and the combine
 // order the kernel has to reproduce: elements fold into the open pane left to right, panes
 // combine oldest first at a firing).

@@ -206,6 +206,49 @@ int main() {
       if (sflags[0] || !total || rows != want) return fail("sliding count window: row count");
     }
   }
+  {
+    // maxBy / minBy (rolling_arg_rows): rolling and count windows of 1 and 7, the same buckets
+    // (one full to its capacity, hole records), an output clamp, three batches. Every winner is a
+    // tag of the batch, -1 (the stored record) or, per key only, -2 (an empty open window).
+    const int a_nsub = 2, a_cap_log2 = 4, a_nsrc = 2;
+    const uint32_t a_bcap = 257, ocap = 300;
+    const size_t a_slots = (size_t)a_nsub << a_cap_log2;
+    const uint32_t windows[3] = {0, 1, 7};
+    for (const uint32_t cw : windows) {
+      std::vector<uint64_t> ak(a_slots, kEmptyKey), aa(a_slots);
+      std::vector<uint32_t> ac(a_slots), aflags(4), acount((size_t)a_nsrc * a_nsub);
+      std::vector<Rec> arecs((size_t)a_nsrc * a_nsub * a_bcap);
+      std::vector<uint64_t> ok(ocap), ov(ocap), wk(arecs.size());
+      std::vector<int64_t> ot(ocap), os(ocap), ws(arecs.size());
+      std::vector<uint32_t> on(1), wn(1);
+      for (int step = 0; step < 3; ++step) {
+        for (int b = 0; b < a_nsrc * a_nsub; ++b) {
+          const uint32_t c = b == 0 ? a_bcap : 100 + 37 * (uint32_t)b;
+          acount[b] = c;
+          for (uint32_t e = 0; e < c; ++e) {
+            Rec& r = arecs[(size_t)b * a_bcap + e];
+            r.key = (uint64_t)(b % a_nsub) * 1000 + e % 5;
+            r.val = (uint64_t)(int64_t)((int)(e % 4) - step);  // ties everywhere
+            r.t = e % 41 == 40 ? 0xFFFFFFFFu : 0;  // a hole
+            r.aux = e;
+          }
+        }
+        on[0] = 0;
+        cpu::rolling_arg_rows(arecs.data(), acount.data(), a_nsrc, a_nsub, a_bcap, a_cap_log2,
+                              AGG_MAX_I64, ak.data(), aa.data(), ac.data(), aflags.data(),
+                              ok.data(), ov.data(), ot.data(), os.data(), on.data(), ocap,
+                              wk.data(), ws.data(), wn.data(), cw);
+        if (wn[0] != 10 || !on[0]) return fail("arg rows: keys touched / rows");
+        for (uint32_t i = 0; i < std::min(on[0], ocap); ++i)
+          if (os[i] < -1 || (step == 0 && os[i] < 0) || (step > 0 && !cw && os[i] != -1))
+            return fail("arg rows: winner of a row");  // (later batches are worse: state wins)
+        for (uint32_t i = 0; i < wn[0]; ++i)
+          if (ws[i] < -2 || (!cw && step > 0 && ws[i] != -1) || (cw == 1 && ws[i] != -2))
+            return fail("arg rows: winner of a key");
+      }
+      if (aflags[0]) return fail("arg rows: flags");
+    }
+  }
   uint64_t chk[kChkN] = {0, 0, 0, 0};
   cpu::check_table(keys_g.data(), nsub, nsub_log2, cap_log2, chk);
   if (chk[kChkMisplaced] || chk[kChkBrokenChain] || chk[kChkDuplicate] || !chk[kChkLive])

@@ -278,6 +278,11 @@ def plan(env, sinks):
                 and meta["key_pos"] is not None:
             _install_native_rolling(env, t, meta)
             continue
+        if meta.get("kind") == "rolling" and meta["agg"] in ("maxBy", "minBy") \
+                and meta["key_pos"] is not None:
+            # (a key selector that is not a position keeps the host RollingReduceOp)
+            _install_native_rolling_by(env, t, meta)
+            continue
         if meta.get("kind") != "window":
             continue
         ws = meta["stream"]
@@ -460,8 +465,36 @@ def _count_window_slide(ws) -> tuple[int, int] | None:
 def _lower_count_window(env, t, ws, spec, meta, children) -> None:
     """keyBy(k).countWindow(n).sum/min/max(p) | reduce(field-wise sum) | aggregate(avg) ->
     NativeCountWindowOp (segmented-scan count windows on the GPU / C++ twin); countWindow(size,
-    slide) with the same functions -> the same operator in its sliding mode."""
+    slide) with the same functions -> the same operator in its sliding mode.
+
+    countWindow(n).maxBy/minBy(p) (tumbling only) -> NativeCountWindowByOp: the arg-select scan
+    names each window's winner and the whole winner record is emitted, so every arity above the
+    key and value positions is accepted and no dead-field condition applies. These keep the host
+    operators: countWindow(size, slide) with maxBy / minBy (the pane ring would need a row per
+    pane), time and session windows with maxBy / minBy (pane state would need the payload row;
+    plan() never lowers their hint), key selectors that are not a position, and a late tag."""
     n, slide = _count_window_size(ws), 0
+    hint = meta.get("native_hint")
+    if hint and hint[0] in ("maxBy", "minBy"):
+        if n is None or ws.keyed is None or ws.keyed.key_pos is None \
+                or ws._late_tag is not None:
+            return
+        from ..runtime.native_ops import NativeCountWindowByOp
+
+        by_kind, by_pos = hint
+        by_key_pos, by_key_fn = ws.keyed.key_pos, ws.keyed.key_fn
+        if by_pos < 0 or by_pos == by_key_pos:
+            return
+        by_fallback, by_device = t.factory, env.config.device
+
+        def by_factory():
+            return NativeCountWindowByOp(count=n, key_fn=by_key_fn, key_pos=by_key_pos,
+                                         val_pos=by_pos, kind=by_kind, device=by_device,
+                                         fallback_factory=by_fallback)
+
+        t.factory = by_factory
+        t.meta = dict(t.meta, native=True)
+        return
     if n is None:
         shape = _count_window_slide(ws)
         if shape is not None:
@@ -706,6 +739,26 @@ def _install_native_rolling(env, t, meta):
                              device=device, fallback_factory=fallback)
         op.device_input, op.event_ts = device_input, event_ts
         return op
+
+    t.factory = factory
+    t.meta = dict(t.meta, native=True)
+
+
+def _install_native_rolling_by(env, t, meta):
+    """keyBy(<field>).maxBy/minBy(p) -> NativeRollingByOp: the arg-select scan names the record
+    that holds each key's extremum and the operator carries that record's row. Key selectors
+    that are not a position keep the host operator."""
+    from ..runtime.native_ops import NativeRollingByOp
+
+    fallback = t.factory
+    device = env.config.device
+    key_fn, key_pos, pos, kind = meta["key_fn"], meta["key_pos"], meta["pos"], meta["agg"]
+    if pos < 0 or pos == key_pos:
+        return
+
+    def factory():
+        return NativeRollingByOp(key_fn=key_fn, key_pos=key_pos, val_pos=pos, kind=kind,
+                                 device=device, fallback_factory=fallback)
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)

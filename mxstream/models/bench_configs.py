@@ -207,6 +207,55 @@ def config11(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 10_000,
             "device": str(dev)}
 
 
+def config12(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 10_000,
+             size: int = 0, by: str | None = None, device: str = "cuda") -> dict:
+    """Keyed rolling max (or with `size` the tumbling ``countWindow(size)`` max) on config 11's
+    data and sort path; with `by` ("max" / "min") the arg-select scan of ``maxBy`` / ``minBy`` on
+    the same data, which also says which record holds the extremum. val_span = 100 over 1,678
+    events per key and step: ties are everywhere. Rows stay on the device; their count is read
+    once at the end."""
+    dev = torch.device(device)
+    if by not in (None, "max", "min"):
+        raise ValueError("config 12: --by max | min")
+    op = KeyedRollingOperator(agg=K.AGG_MIN_I64 if by == "min" else K.AGG_MAX_I64, device=dev,
+                              max_keys=keys, batch_capacity=batch, count_window=size,
+                              arg_select=by is not None)
+    op.sort_free = False
+    kt = torch.empty(batch, dtype=torch.int64, device=dev)
+    tt = torch.empty_like(kt)
+    vt = torch.empty_like(kt)
+    step_i = [0]
+    fired = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def step():
+        K.gen_events(kt, tt, vt, seed=2, stream_id=0, idx0=step_i[0] * batch, nkeys=keys,
+                     ts_base=0, ts_span=1000, disorder=0, val_lo=0, val_span=100)
+        fired.add_(op.process(kt, vt, to_host=False))
+        step_i[0] += 1
+
+    for _ in range(warmup):
+        step()
+    fired.zero_()
+    _sync(dev)
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    _sync(dev)
+    dt = time.perf_counter() - t0
+    op.check()
+    r = {"config": 12, "scan": f"arg-select ({by}By)" if by else "value (max)",
+         "window": f"countWindow({size})" if size else "rolling",
+         "metric": f"events/sec (keyed {'count-window' if size else 'rolling'} "
+                   f"{by or 'max'}{'By' if by else ''}, {keys // 1000}k keys, radix-sort path)",
+         "value": batch * steps / dt, "unit": "events/s", "ms_per_step": dt / steps * 1e3,
+         "rows": int(fired.item()), "keys": keys, "events_per_step": batch, "device": str(dev)}
+    if by:
+        # rows whose winner was the record already held in state, in the last step
+        n = min(op.check(), op.out_src.numel())
+        r["stored_winner_rows_last_step"] = int((op.out_src[:n] == -1).sum().item())
+    return r
+
+
 def config2_spill(steps: int, warmup: int, batch: int = 1 << 22, active: int = 500_000,
                   drift: int = 50_000, table_keys: int = 1_000_000, revisit: float = 0.01,
                   device: str = "cuda") -> dict:
@@ -1050,7 +1099,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1079,7 +1128,11 @@ def main(argv=None) -> int:
     ap.add_argument("--sort-path", action="store_true",
                     help="config 2: the radix-sort rolling path instead of the sort-free one")
     ap.add_argument("--keys", type=int, default=None, help="config 2: key space (default 10k)")
-    ap.add_argument("--size", type=int, default=100, help="config 11: count-window size")
+    ap.add_argument("--size", type=int, default=None,
+                    help="config 11: count-window size (default 100); config 12: the tumbling "
+                         "countWindow(size) instead of the rolling aggregate")
+    ap.add_argument("--by", choices=["max", "min"], default=None,
+                    help="config 12: the arg-select scan of maxBy / minBy instead of the plain max")
     ap.add_argument("--slide", type=int, default=None,
                     help="config 11: count-window slide (omitted: the tumbling countWindow(size))")
     ap.add_argument("--latency-fire", type=int, default=0,
@@ -1123,8 +1176,11 @@ def main(argv=None) -> int:
         r = config10(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 1_000_000,
                      device=a.device, top_n=a.top_n)
     elif a.config == 11:
-        r = config11(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 10_000, size=a.size,
-                     slide=a.slide, device=a.device)
+        r = config11(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 10_000,
+                     size=a.size or 100, slide=a.slide, device=a.device)
+    elif a.config == 12:
+        r = config12(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 10_000,
+                     size=a.size or 0, by=a.by, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

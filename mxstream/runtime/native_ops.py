@@ -9,6 +9,9 @@ tests/test_api_native.py); the planner (api/planner.py) only selects it for shap
 Records are columnarised per micro-batch: the key field becomes a 64-bit id (string keys via the
 C++ StringDict), the aggregated field an int64 / float64 column, the timestamp an int64 column;
 window results come back as (key id, value, count) rows and are rebuilt into tuples.
+
+``NativeRollingByOp`` / ``NativeCountWindowByOp`` run ``maxBy`` / ``minBy`` on the arg-select
+engine and carry each key's current winner row (docs/DESIGN.md §15.2).
 """
 from __future__ import annotations
 
@@ -1296,6 +1299,274 @@ class NativeCountWindowOp(NativeRollingOp):
                 self._to_fallback()
                 return self.fallback.process(expand_columns(recs))
         return super()._run(recs)
+
+
+class DeviceWinners(DeviceTemplates):
+    """Current-winner rows of ``maxBy`` / ``minBy`` keys on the device: one column per field
+    other than the key (the compared field included), indexed by dictionary id, plus each key's
+    output subtask. Single rank only (records reach a key's owner through the executor's keyed
+    exchange, so the table is never replicated)."""
+
+    def __init__(self, kinds, key_pos: int, val_pos: int, device):
+        super().__init__(kinds, key_pos, val_pos, device, None)
+
+    def _grow(self, need: int) -> None:
+        vp, self.val_pos = self.val_pos, -1  # (the base class keeps no column for the value)
+        try:
+            super()._grow(need)
+        finally:
+            self.val_pos = vp
+
+    def prepare(self, nkeys: int, jhash, ctx) -> None:
+        self._grow(max(nkeys, 1))
+        if jhash is not None:
+            self._subtasks(nkeys, jhash, ctx)
+
+    def rows(self, cb, n: int, key: torch.Tensor, src: torch.Tensor) -> list:
+        """Output columns: the batch's record at `src` where src >= 0, else the key's stored
+        winner row (read before `update`)."""
+        fresh = src >= 0
+        at = torch.where(fresh, src & 0xFFFFFFFF, torch.zeros_like(src))
+        cols = []
+        for j in range(len(self.kinds)):
+            if j == self.key_pos:
+                cols.append(key.to(torch.int32))
+            else:
+                t = self.tpl[j]
+                cols.append(torch.where(fresh, cb.cols[j][:n].to(t.dtype)[at], t[key]))
+        return cols
+
+    def update(self, cb, n: int, win_key: torch.Tensor, win_src: torch.Tensor) -> None:
+        """Stored row of every key in win_key <- the batch record at win_src where that is >= 0
+        (a scatter; the keys of a batch's segments are distinct)."""
+        fresh = win_src >= 0
+        at = torch.where(fresh, win_src & 0xFFFFFFFF, torch.zeros_like(win_src))
+        for j, t in self.tpl.items():
+            t[win_key] = torch.where(fresh, cb.cols[j][:n].to(t.dtype)[at], t[win_key])
+
+
+class _ByRows:
+    """``maxBy(p)`` / ``minBy(p)`` on the arg-select engine (KeyedRollingOperator with
+    ``arg_select``): the engine says which record holds the extremum (a tag into the batch, or -1
+    for the record already held in state), and this operator carries the winner's ROW -- the
+    keep-first template of ``max(p)`` becomes a current-winner row per key, replaced after every
+    batch by the batch record the engine names. The whole winner record is emitted. Ties keep
+    the earlier record (Flink's ``maxBy(pos)``, first = true).
+
+    Row path (tuples, host column batches): ``self.templates`` is the dict key id -> winner
+    tuple. Device path (device batches with dictionary keys): a DeviceWinners table; a NaN in the
+    compared column has no place in the order and is NOT detected there (no sync to look for it).
+    On the host paths a NaN, like a mixed-type batch, goes to the host operator before any native
+    state exists and raises afterwards. More than one rank: the executor's keyed exchange brings
+    every record to its key's owner and each rank runs its local engine (never the operator's own
+    device exchange)."""
+
+    _started = False  # the engine holds state: unsupported data can no longer fall back
+
+    def open(self, ctx):
+        di, self.device_input = self.device_input, None  # (never the collective device route)
+        try:
+            super().open(ctx)
+        finally:
+            self.device_input = di
+
+    def _make_engine(self, v, count: int) -> bool:
+        from .rolling_operator import KeyedRollingOperator
+
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            return False
+        self.is_float = isinstance(v, float)
+        agg = {("maxBy", False): K.AGG_MAX_I64, ("maxBy", True): K.AGG_MAX_F64,
+               ("minBy", False): K.AGG_MIN_I64, ("minBy", True): K.AGG_MIN_F64}[(self.kind, self.is_float)]
+        self.op = KeyedRollingOperator(agg=agg, device=torch.device(self.device),
+                                       max_keys=self.max_keys, parallelism=1, batch_capacity=1024,
+                                       count_window=count, arg_select=True)
+        return True
+
+    def _unsupported(self, recs: list) -> list:
+        if self._started:
+            raise TypeError("native maxBy / minBy: unsupported data (mixed types, NaN) after "
+                            "native state exists")
+        self._to_fallback()
+        return self.fallback.process(recs)
+
+    def _by_out(self, rows, value_of, ts_of) -> list:
+        """Engine rows -> the winners' records in input order, then the stored rows move on."""
+        from ..utils.hashing import flink_murmur
+
+        self._started = True
+        order = np.argsort(rows.tags & 0xFFFFFFFF, kind="stable")
+        P, MP = self.ctx.parallelism, self.ctx.max_parallelism
+        subs: dict = {}
+        out = []
+        for k, src, i in zip(rows.keys[order].tolist(), rows.srcs[order].tolist(),
+                             (rows.tags[order] & 0xFFFFFFFF).tolist()):
+            sub = subs.get(k)
+            if sub is None:
+                key_obj = self.dict.get(k) if self.str_keys else k
+                sub = subs[k] = (flink_murmur(java_hash(key_obj)) % MP) * P // MP
+            row = value_of(src & 0xFFFFFFFF) if src >= 0 else self.templates[k]
+            out.append(Rec(row, self._out_ts(ts_of(i)), sub))
+        for k, src in zip(rows.win_keys.tolist(), rows.win_srcs.tolist()):
+            if src >= 0:
+                self.templates[k] = value_of(src & 0xFFFFFFFF)
+        return out
+
+    def _run(self, recs: list) -> list:
+        if not recs:
+            return []
+        if all(isinstance(r, ColumnBatch) for r in recs):
+            return self._run_columns(recs)
+        recs = expand_columns(recs)
+        try:
+            v0 = recs[0].value
+            if not isinstance(v0, tuple) or len(v0) <= max(self.key_pos, self.val_pos):
+                raise TypeError("record shape")
+            if self.op is None and not self._build(v0[self.val_pos]):
+                raise TypeError("unsupported value")
+            n, ar = len(recs), len(v0)
+            kid = np.empty(n, dtype=np.int64)
+            vv = np.empty(n, dtype=np.float64 if self.is_float else np.int64)
+            for i, r in enumerate(recs):
+                v = r.value
+                if not isinstance(v, tuple) or len(v) != ar:
+                    raise TypeError("record shape")
+                kid[i] = self._key_id(v[self.key_pos])
+                x = v[self.val_pos]
+                if isinstance(x, bool) or isinstance(x, float) != self.is_float or \
+                        not isinstance(x, (int, float)):
+                    raise TypeError("mixed value types")
+                vv[i] = x
+            if self.is_float and np.isnan(vv).any():
+                raise TypeError("NaN in the compared field")
+        except (TypeError, OverflowError):
+            return self._unsupported(recs)
+        dev = self.op.device
+        rows = self.op.process(torch.from_numpy(kid).to(dev),
+                               torch.from_numpy(vv.view(np.int64)).to(dev))
+        return self._by_out(rows, lambda i: recs[i].value, lambda i: recs[i].ts)
+
+    def _device_ok(self, batches: list) -> bool:
+        return NativeRollingOp._device_ok(self, batches)
+
+    def _run_columns(self, batches: list) -> list:
+        if self._device_ok(batches) and (self.dtpl is not None or not self._started):
+            b0 = batches[0]
+            if b0.strings is not self.dict:
+                if len(self.dict) and self.dtpl is None:
+                    return self._run_columns([b.host() for b in batches])
+                self.dict = b0.strings
+            self.str_keys = True
+            vk = b0.kinds[self.val_pos]
+            if self.op is None and not self._build(1.0 if vk == FK_DOUBLE else 1):
+                raise TypeError("unsupported value")
+            if (vk == FK_DOUBLE) != self.is_float:
+                raise TypeError("mixed value types")
+            if self.dtpl is None:
+                self.dtpl = DeviceWinners(b0.kinds, self.key_pos, self.val_pos, self.op.device)
+            return self._run_device(batches)
+        batches = [b.host() if isinstance(b, DeviceColumnBatch) else b for b in batches]
+        try:
+            cb = self._cb_concat(batches)
+            vk = cb.kinds[self.val_pos] if len(cb.kinds) > self.val_pos else FK_STR
+            if vk == FK_STR or len(cb.kinds) <= max(self.key_pos, self.val_pos) or cb.scalar:
+                raise TypeError("value column not numeric")
+            if self.op is None:
+                if not self._build(1.0 if vk == FK_DOUBLE else 1):
+                    raise TypeError("unsupported value")
+            elif (vk == FK_DOUBLE) != self.is_float:
+                raise TypeError("mixed value types")
+            kid = self._cb_keys(cb)
+            vv = cb.cols[self.val_pos].astype(np.float64 if self.is_float else np.int64,
+                                              copy=False)
+            if self.is_float and np.isnan(vv).any():
+                raise TypeError("NaN in the compared field")
+        except TypeError:
+            return self._unsupported(expand_columns(batches))
+        dev = self.op.device
+        rows = self.op.process(torch.from_numpy(np.ascontiguousarray(kid, dtype=np.int64)).to(dev),
+                               torch.from_numpy(np.ascontiguousarray(vv).view(np.int64)).to(dev))
+        ts = cb.ts.tolist() if cb.ts is not None else None
+        return self._by_out(rows, cb.value,
+                            (lambda i: ts[i]) if ts is not None else (lambda i: LONG_MIN))
+
+    def _run_device(self, batches: list) -> list:
+        """Device batches with dictionary keys: keys and values go to the engine in place; the
+        output is ONE device column batch in arrival order whose columns are
+        ``where(src >= 0, col[src], table[key])``, read before the table takes the batch's
+        winners (a scatter of ``col[win_src]`` at ``win_key``). One host read per batch, the
+        engine's flags and counts, as on the ``max(p)`` path."""
+        cb = concat_device(batches)
+        n = cb.n
+        op = self.op
+        kid = cb.cols[self.key_pos][:n].to(torch.int64)
+        v = cb.cols[self.val_pos][:n]
+        vals = v.view(torch.int64) if v.dtype == torch.float64 else v.to(torch.int64)
+        self.dtpl.prepare(len(self.dict), self._jhash_dev(), self.ctx)
+        op.process(kid.contiguous(), vals.contiguous(), to_host=False)
+        self._started = True
+        hf = torch.cat((op.flags, op.n_buf)).tolist()
+        k = min(op._check_flags(hf[:4]), op.out_key.numel())
+        nw = hf[5]
+        out = []
+        if k:
+            tag = op.out_tag[:k]
+            order = torch.argsort(tag)  # arrival order
+            key = op.out_key[:k][order]
+            cols = self.dtpl.rows(cb, n, key, op.out_src[:k][order])
+            ts = None
+            if cb.ts is not None:
+                ts = self._device_ts(cb.ts[:n], tag[order] & 0xFFFFFFFF)
+            out = [DeviceColumnBatch(k, cols, self.dtpl.kinds, self.dict, ts,
+                                     sub_dev=self.dtpl.sub[key])]
+        if nw:
+            self.dtpl.update(cb, n, op.win_key[:nw], op.win_src[:nw])
+        return out
+
+    def _device_ts(self, ts: torch.Tensor, at: torch.Tensor) -> torch.Tensor:
+        return ts[at]
+
+    def snapshot(self) -> dict:
+        snap = super().snapshot()
+        if "fallback" not in snap:
+            snap["started"] = self._started
+        return snap
+
+    def restore(self, snap: dict) -> None:
+        dt = snap.get("device_templates")
+        if dt is not None and self.dtpl is None and "fallback" not in snap:
+            if self.op is None:
+                self._build(1.0 if snap["is_float"] else 1)
+            self.dtpl = DeviceWinners(tuple(dt["kinds"]), self.key_pos, self.val_pos,
+                                      self.op.device)
+        super().restore(snap)
+        self._started = bool(snap.get("started", False))
+
+
+class NativeRollingByOp(_ByRows, NativeRollingOp):
+    """``keyBy(k).maxBy(p)`` / ``minBy(p)``: every record emits the key's current winner record
+    (see _ByRows). Output order equals input order."""
+
+    def _build(self, v) -> bool:
+        return self._make_engine(v, 0)
+
+
+class NativeCountWindowByOp(_ByRows, NativeCountWindowOp):
+    """``keyBy(k).countWindow(n).maxBy(p)`` / ``minBy(p)`` (tumbling): the element that completes
+    a key's window emits the window's winner record, with the GlobalWindow's timestamp. The open
+    window's leader is the stored row; a new window starts empty. Every arity above the key and
+    value positions is accepted (the whole record is emitted: no dead-field condition).
+    ``countWindow(size, slide)`` keeps the host operator: the pane ring would need a row per
+    pane."""
+
+    def __init__(self, *, count: int, **kw):
+        super().__init__(count=count, result_builder=None, ok_arities=None, slide=0, **kw)
+
+    def _build(self, v) -> bool:
+        return self._make_engine(v, self.count)
+
+    def _device_ts(self, ts: torch.Tensor, at: torch.Tensor) -> torch.Tensor:
+        return torch.full_like(at, LONG_MAX)  # GlobalWindow.maxTimestamp()
 
 
 class NativeSessionOp(NativeWindowOp):

@@ -11,6 +11,10 @@ sequential twin ``rolling_rows``. Output rows are in per-key arrival order.
 Count windows run on the same passes: tumbling ``countWindow(n)`` as a segmented rolling_scan,
 sliding ``countWindow(n, s)`` as rolling_slide_scan over panes of gcd(n, s) elements (CPU twin
 ``rolling_slide_rows``), see docs/DESIGN.md §15.
+
+``arg_select`` (maxBy / minBy, rolling or tumbling count windows): rolling_argscan scans the pair
+(value, winner tag) and names the record that holds each extremum (CPU twin ``rolling_arg_rows``),
+see docs/DESIGN.md §15.2.
 """
 from __future__ import annotations
 
@@ -41,6 +45,12 @@ class RollingRows:
     values: np.ndarray  # int64 raw (f64 bit pattern for float aggregates; count for COUNT)
     tags: np.ndarray   # int64: src rank << 32 | index in that rank's batch
     counts: np.ndarray | None = None  # uint32 elements per window (sliding count windows only)
+    # arg_select only: per row the winning record's tag (-1: the record already held in state),
+    # and per key touched by the batch the winner of its state after the batch (a tag, -1 the
+    # stored record, -2 count windows with an empty open window)
+    srcs: np.ndarray | None = None      # int64
+    win_keys: np.ndarray | None = None  # uint64
+    win_srcs: np.ndarray | None = None  # int64
 
 
 class KeyedRollingOperator:
@@ -49,7 +59,8 @@ class KeyedRollingOperator:
                  max_parallelism: int = 128, batch_capacity: int = 1 << 20,
                  cap_log2: int | None = None, filter_prog: E.Program = E.EMPTY, emit_capacity: int | None = None,
                  count_window: int = 0, dense_keys: bool = False, spill: bool = False,
-                 spill_load: float = 0.75, spill_target: float = 0.5, count_slide: int = 0):
+                 spill_load: float = 0.75, spill_target: float = 0.5, count_slide: int = 0,
+                 arg_select: bool = False):
         """count_window = n > 0: tumbling count windows instead of a rolling aggregate
         (``keyBy(..).countWindow(n)`` with an incremental reduce/aggregate: GlobalWindows +
         PurgingTrigger(CountTrigger(n)), chapter2/README.md:78) -- a row is emitted when a key's
@@ -72,7 +83,16 @@ class KeyedRollingOperator:
         `spill_target` (the table is rebuilt without them). A batch whose keys include spilled
         ones first promotes them back (their (acc, count) re-inserted into HBM), so every record
         is still folded by the GPU pass in arrival order. The headroom (1 - spill_load) must hold
-        one micro-batch's new keys."""
+        one micro-batch's new keys.
+
+        arg_select: maxBy / minBy (the four MIN / MAX aggregates, rolling or tumbling count
+        windows): the scan also says WHICH record holds the extremum. Every row carries the
+        winner's tag in ``out_src`` (-1: the record already held in state); a later record wins
+        only if it is strictly better, so ties keep the earlier one (Flink's first = true). For
+        every key of the batch ``win_key`` / ``win_src`` (``win_n`` of them) give the winner of
+        its state after the batch (-2: count windows, the open window is empty). The rows that
+        the tags name are the caller's: the engine keeps values only. Sort path only; no filter,
+        no spill tier, no dense ids, no sliding count windows."""
         self.device = K.resolve_device(device)
         self.comm = comm or LocalComm()
         self.world, self.rank = self.comm.world, self.comm.rank
@@ -83,6 +103,15 @@ class KeyedRollingOperator:
         if agg in (K.AGG_AVG_F64, K.AGG_AVG_I64) and not self.count_window:
             raise ValueError("rolling avg is not a Flink rolling aggregate")
         self.count_slide = int(count_slide)
+        self.arg_select = bool(arg_select)
+        if self.arg_select:
+            if agg not in (K.AGG_MAX_I64, K.AGG_MIN_I64, K.AGG_MAX_F64, K.AGG_MIN_F64):
+                raise ValueError("arg_select: min / max aggregates only")
+            if spill or dense_keys or count_slide:
+                raise ValueError("arg_select: hashed HBM state, rolling or tumbling count "
+                                 "windows only (no spill tier, no dense ids, no count_slide)")
+            if filter_prog.as_args()[0]:
+                raise ValueError("arg_select: no fused filter (filter_prog)")
         self.ppw = 0
         if self.count_slide:
             if self.count_slide < 0 or self.count_slide >= (1 << 31):
@@ -157,7 +186,7 @@ class KeyedRollingOperator:
         # Sort-free COUNT path (rolling_hist) when the table fits its LDS counter; False forces
         # the sort path (A/B, tests).
         # (the spill tier tracks slots through the sort path; sliding count windows scan panes)
-        self.sort_free = not self.spill and not self.count_slide
+        self.sort_free = not self.spill and not self.count_slide and not self.arg_select
         self._hist_tmp = None
         if self.dense:
             code, consts = filter_prog.as_args()
@@ -193,6 +222,13 @@ class KeyedRollingOperator:
         self.out_tag = torch.empty(ocap, dtype=torch.int64, device=dev)
         self.out_cnt = (torch.empty(ocap, dtype=torch.int32, device=dev)
                         if self.count_slide else None)
+        if self.arg_select:
+            # one (win_key, win_src) pair per key segment of the batch; their number is the
+            # segment count n_buf[1] (the GPU's n_heads; the CPU twin writes it)
+            self.out_src = torch.empty(ocap, dtype=torch.int64, device=dev)
+            self.win_key = torch.empty(total, dtype=torch.int64, device=dev)
+            self.win_src = torch.empty(total, dtype=torch.int64, device=dev)
+            self.win_n = self.n_buf[1:2]
         # flags[2] is the emitted-row cursor: one D2H returns the row count with the table-full
         # (bit0) and reserved-key (bit2) flags of flags[0].
         self.out_n = self.flags[2:3]
@@ -252,6 +288,9 @@ class KeyedRollingOperator:
         if self.count_slide:
             self._slide_scan(m, sk, n_in, min(n, self.nslots), code, consts, cap, shift, shift, st)
             return self._emit(to_host)
+        if self.arg_select:
+            self._arg_scan(m, sk, n_in, min(n, self.nslots), cap, shift, shift, st)
+            return self._emit(to_host)
         m.gpu_rolling_scan(self.agg, sk.data_ptr(), 0, self.vals_out.data_ptr(), n_in.data_ptr(),
                            self.heads.data_ptr(), self.n_buf[1:2].data_ptr(),
                            min(n, self.nslots), self.acc_g.data_ptr(), self.cnt_g.data_ptr(),
@@ -271,6 +310,16 @@ class KeyedRollingOperator:
                                  self.out_tag.data_ptr(), self.out_cnt.data_ptr(),
                                  self.out_n.data_ptr(), cap, abits, shift, st, self.count_window,
                                  self.count_slide)
+
+    def _arg_scan(self, m, sk, n_in, max_segments, cap, abits, shift, st):
+        """The arg-select scan over the sorted batch (rolling_argscan_kernel)."""
+        m.gpu_rolling_argscan(self.agg, sk.data_ptr(), self.vals_out.data_ptr(), n_in.data_ptr(),
+                              self.heads.data_ptr(), self.n_buf[1:2].data_ptr(), max_segments,
+                              self.acc_g.data_ptr(), self.cnt_g.data_ptr(), self.keys_g.data_ptr(),
+                              self.out_key.data_ptr(), self.out_val.data_ptr(),
+                              self.out_tag.data_ptr(), self.out_src.data_ptr(),
+                              self.out_n.data_ptr(), cap, self.win_key.data_ptr(),
+                              self.win_src.data_ptr(), abits, shift, st, self.count_window)
 
     def process(self, keys: torch.Tensor, vals: torch.Tensor, to_host: bool = True):
         """Update state with one micro-batch; returns the emitted rows (host) or the device count."""
@@ -353,6 +402,9 @@ class KeyedRollingOperator:
                     self._slide_scan(m, sk, n_in, min(total, self.nslots), code, consts, cap,
                                      abits, shift, st)
                     return self._emit(to_host)
+                if self.arg_select:
+                    self._arg_scan(m, sk, n_in, min(total, self.nslots), cap, abits, shift, st)
+                    return self._emit(to_host)
                 m.gpu_rolling_scan(self.agg, sk.data_ptr(), 0,
                                    self.vals_out.data_ptr(), n_in.data_ptr(), self.heads.data_ptr(),
                                    self.n_buf[1:2].data_ptr(), min(total, self.nslots),
@@ -371,6 +423,16 @@ class KeyedRollingOperator:
                                      self.out_tag.data_ptr(), self.out_cnt.data_ptr(),
                                      self.out_n.data_ptr(), cap, self.count_window,
                                      self.count_slide)
+        elif self.arg_select:
+            m.cpu_rolling_arg_rows(self.recv.data_ptr(), self.recv_counts.data_ptr(), self.world,
+                                   self.nsub, self.bucket_cap, self.cap_log2, self.agg,
+                                   self.keys_g.data_ptr(), self.acc_g.data_ptr(),
+                                   self.cnt_g.data_ptr(), self.flags.data_ptr(),
+                                   self.out_key.data_ptr(), self.out_val.data_ptr(),
+                                   self.out_tag.data_ptr(), self.out_src.data_ptr(),
+                                   self.out_n.data_ptr(), cap, self.win_key.data_ptr(),
+                                   self.win_src.data_ptr(), self.win_n.data_ptr(),
+                                   self.count_window)
         else:
             m.cpu_rolling_rows(self.recv.data_ptr(), self.recv_counts.data_ptr(), self.world,
                                self.nsub, self.bucket_cap, self.cap_log2, self.agg,
@@ -501,6 +563,8 @@ class KeyedRollingOperator:
     def _emit(self, to_host: bool):
         if not to_host:
             return self.out_n
+        if self.arg_select:
+            return self._emit_arg()
         # (the slab copy moves 16-byte granules: the uint32 count column needs 4 rows each)
         if self.device.type == "cuda" and \
                 self.out_key.numel() % (4 if self.count_slide else 2) == 0:
@@ -528,6 +592,18 @@ class KeyedRollingOperator:
                            self.out_tag[:k].cpu().numpy().copy(),
                            self.out_cnt[:k].cpu().numpy().copy().view(np.uint32)
                            if self.count_slide else None)
+
+    def _emit_arg(self) -> RollingRows:
+        """arg_select rows and per-key winners on the host (one read of the flags and counts)."""
+        hf = torch.cat((self.flags, self.n_buf)).tolist()
+        k = min(self._check_flags(hf[:4]), self.out_key.numel())
+        nw = hf[5]
+
+        def host(t, m):
+            return t[:m].cpu().numpy().copy()
+        return RollingRows(host(self.out_key, k).view(np.uint64), host(self.out_val, k),
+                           host(self.out_tag, k), None, host(self.out_src, k),
+                           host(self.win_key, nw).view(np.uint64), host(self.win_src, nw))
 
     def _dummy_ts(self, n: int) -> torch.Tensor:
         t = getattr(self, "_ts0", None)
@@ -568,6 +644,8 @@ class KeyedRollingOperator:
         kg = K.keygroups(keys, max_parallelism=self.max_parallelism).cpu().numpy()
         meta = {"kind": "rolling", "agg": self.agg, "records_in": self.records_in,
                 "steps": self.steps, "count_window": self.count_window}
+        if self.arg_select:
+            meta["arg_select"] = True
         if self.count_slide:
             # the ordinal and the pane ring, one column per ring position (pane p at p % ppw)
             meta["count_slide"] = self.count_slide
@@ -579,8 +657,10 @@ class KeyedRollingOperator:
 
     def restore_state(self, rows: dict, meta: dict) -> None:
         if meta["agg"] != self.agg or meta.get("count_window", 0) != self.count_window \
-                or meta.get("count_slide", 0) != self.count_slide:
-            raise ValueError("checkpoint aggregate / count window does not match the operator")
+                or meta.get("count_slide", 0) != self.count_slide \
+                or bool(meta.get("arg_select", False)) != self.arg_select:
+            raise ValueError("checkpoint aggregate / count window / arg-select mode does not "
+                             "match the operator")
         self.records_in, self.steps = meta["records_in"], meta["steps"]
         self.keys_g.fill_(-1)
         self.acc_g.zero_()
