@@ -1,8 +1,9 @@
 // mxstream — host sanitizer harness. Built by `python -m mxstream.build
 // --sanitize` with -fsanitize=address,undefined (and -fno-sanitize-recover) against the C++ twins
 // of the kernels, then driven through a few micro-batches of the keyed window pipeline
-// (partition -> window_agg -> fire), the vector-metric windows and the table checker, on
-// adversarial shapes: tiny sub-tables, late data, bucket counts at capacity, empty batches.
+// (partition -> window_agg -> fire), the vector-metric windows, the window-join twins and the
+// table checker, on adversarial shapes: tiny sub-tables, late data, bucket counts at capacity,
+// empty batches, unmatched join keys on both ends, every chunking of an expanded pair range.
 // Exit code 0 and no sanitizer report = pass (tests/test_debug.py).
 #include <algorithm>
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "mxs_check.h"
+#include "mxs_join.h"
 #include "mxs_kernels.h"
 #include "mxs_vector.h"
 
@@ -248,6 +250,61 @@ int main() {
       }
       if (aflags[0]) return fail("arg rows: flags");
     }
+  }
+  {
+    // Window join twins (mxs_join.h): matched and unmatched keys on both ends, every pair range
+    // of a chunked expand against the nested loop, and a firing without a common key (P = 0).
+    const std::vector<int64_t> lk = {1, 3, 4, 5, 9, 10, 12}, ll = {2, 1, 3, 2, 1, 4, 2};
+    const std::vector<int64_t> rk = {0, 3, 5, 6, 7, 10, 11}, rl = {1, 2, 3, 1, 1, 2, 5};
+    std::vector<int64_t> lh(lk.size()), rh(rk.size());
+    int64_t lt = 0, rt = 0;
+    for (size_t i = 0; i < lk.size(); ++i) lh[i] = lt, lt += ll[i];
+    for (size_t i = 0; i < rk.size(); ++i) rh[i] = rt, rt += rl[i];
+    std::vector<uint64_t> lo(lt), ro(rt);
+    for (int64_t i = 0; i < lt; ++i) lo[i] = f64_order_bits((uint64_t)(1000 + i));
+    for (int64_t i = 0; i < rt; ++i) ro[i] = f64_order_bits((uint64_t)(2000 + i));
+    const JoinSide L{lk.data(), lh.data(), (int64_t)lk.size(), lt};
+    const JoinSide R{rk.data(), rh.data(), (int64_t)rk.size(), rt};
+    const int64_t kl = L.nseg;
+    std::vector<int64_t> match(kl), off(kl + 1), plan(kJoinPlanCols * (kl + 1)), meta(kJoinMeta);
+    std::vector<uint64_t> cnt(kl);
+    cpu::join_match(L, R, match.data(), cnt.data());
+    cpu::join_scan(L, R, match.data(), cnt.data(), off.data(), plan.data(), meta.data());
+    std::vector<int64_t> want;  // the nested loop: (key, left, right) rows
+    for (int64_t i = 0; i < kl; ++i)
+      for (size_t j = 0; j < rk.size(); ++j)
+        if (rk[j] == lk[i])
+          for (int64_t a = 0; a < ll[i]; ++a)
+            for (int64_t b = 0; b < rl[j]; ++b) {
+              want.push_back(lk[i]);
+              want.push_back(1000 + lh[i] + a);
+              want.push_back(2000 + rh[j] + b);
+            }
+    const int64_t P = meta[kJoinP];
+    if (P != (int64_t)want.size() / 3 || P != 16 || meta[kJoinM] != 3 || meta[kJoinErr] ||
+        match[0] != -1 || match[kl - 1] != -1 || off[kl] != P)
+      return fail("join: match / scan");
+    for (int64_t chunk = 1; chunk <= P + 1; ++chunk)
+      for (int64_t p0 = 0; p0 < P; p0 += chunk) {
+        const int64_t p1 = std::min(P, p0 + chunk), m = p1 - p0;
+        std::vector<int64_t> ok(m), ol(m), orr(m);  // exactly the range: a write past it is caught
+        cpu::join_expand(L, R, match.data(), off.data(), lo.data(), ro.data(), p0, p1, ok.data(),
+                         ol.data(), orr.data());
+        for (int64_t p = p0; p < p1; ++p)
+          if (ok[p - p0] != want[3 * p] || ol[p - p0] != want[3 * p + 1] ||
+              orr[p - p0] != want[3 * p + 2])
+            return fail("join: expanded range");
+      }
+    const std::vector<int64_t> ok2 = {2, 8}, oh2 = {0, 1};
+    const JoinSide R2{ok2.data(), oh2.data(), 2, 2}, E{nullptr, nullptr, 0, 0};
+    cpu::join_match(L, R2, match.data(), cnt.data());
+    cpu::join_scan(L, R2, match.data(), cnt.data(), off.data(), plan.data(), meta.data());
+    if (meta[kJoinP] != 0 || meta[kJoinM] != 0 || off[kl] != 0) return fail("join: P = 0");
+    cpu::join_expand(L, R2, match.data(), off.data(), lo.data(), ro.data(), 0, 0, nullptr, nullptr,
+                     nullptr);
+    cpu::join_match(E, R, nullptr, nullptr);
+    cpu::join_scan(E, R, nullptr, nullptr, off.data(), plan.data(), meta.data());
+    if (meta[kJoinP] != 0 || off[0] != 0) return fail("join: empty side");
   }
   uint64_t chk[kChkN] = {0, 0, 0, 0};
   cpu::check_table(keys_g.data(), nsub, nsub_log2, cap_log2, chk);

@@ -92,6 +92,20 @@ class DataStream:
         t = Transformation(next(_ids), "Union", "union", [self.t] + [o.t for o in others])
         return DataStream(self.env, t)
 
+    def join(self, other: "DataStream"):
+        """Window join (api/joins.py): ``a.join(b).where(k).equal_to(k).window(w).apply(fn)``."""
+        from .joins import JoinedStreams
+
+        return JoinedStreams(self, other)
+
+    def co_group(self, other: "DataStream"):
+        """Window co-group: ``...apply(fn(lefts, rights, out))``, the primitive under ``join``."""
+        from .joins import CoGroupedStreams
+
+        return CoGroupedStreams(self, other)
+
+    coGroup = co_group
+
     def rebalance(self) -> "DataStream":
         return self._one_input("Rebalance", lambda: O.RebalanceOp(self.env.config.rebalance_start))
 

@@ -131,6 +131,31 @@ class ReduceFunction(Function):
         raise NotImplementedError
 
 
+class JoinFunction(Function):
+    """join(left, right) -> value, once per pair of a (key, window) (JoinedStreams.apply)."""
+
+    def join(self, left, right):
+        raise NotImplementedError
+
+
+class FlatJoinFunction(Function):
+    """join(left, right, out): any number of values per pair."""
+
+    def join(self, left, right, out: "Collector"):
+        raise NotImplementedError
+
+
+class CoGroupFunction(Function):
+    """co_group(lefts, rights, out): both sides' elements of a (key, window), each in arrival
+    order; either list may be empty (CoGroupedStreams.apply)."""
+
+    def co_group(self, lefts, rights, out: "Collector"):
+        raise NotImplementedError
+
+    def coGroup(self, lefts, rights, out):
+        return self.co_group(lefts, rights, out)
+
+
 class AggregateFunction(Function):
     """createAccumulator / add / getResult / merge (ComputeCpuAvg.java:33-58)."""
 

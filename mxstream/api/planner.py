@@ -14,6 +14,11 @@ runs:
     output reads just the key and the aggregate (BandwidthMonitorWithEventTime.java:48-53),
     or the tuple has no such fields.
 
+A window join (api/joins.py) whose function is a projection -- a tuple of the key and one value
+field of each side -- over tumbling / sliding event-time windows with both keys given as field
+positions is lowered onto NativeJoinOp (``_lower_join``); any other join, and every co-group,
+keeps the host plan (tagged union -> keyed window -> co-group function).
+
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
 (``_lower_topn``): the keyed operator cuts each firing to its top-N candidates on the device.
 """
@@ -282,6 +287,9 @@ def plan(env, sinks):
                 and meta["key_pos"] is not None:
             # (a key selector that is not a position keeps the host RollingReduceOp)
             _install_native_rolling_by(env, t, meta)
+            continue
+        if meta.get("kind") == "join":
+            _lower_join(env, t, meta)
             continue
         if meta.get("kind") != "window":
             continue
@@ -762,3 +770,91 @@ def _install_native_rolling_by(env, t, meta):
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)
+
+
+_JOIN_RIGHT = 100  # variable ids of the right row's fields in a traced join function
+
+
+def trace_join_projection(fn, key_pos, al: int, ar: int):
+    """Trace `fn(left, right)` over rows of arity `al` / `ar`. Returns (layout, left value field,
+    right value field) when the result is a tuple whose every field is a bare key reference (of
+    either side: "k") or a bare reference to the one non-key field of its side ("l" / "r"), and
+    both sides' values appear; None otherwise (arithmetic, a non-tuple result, a second value
+    field of one side, a flat join function, a function that does not trace)."""
+    from .joins import _is_flat_join
+
+    if _is_flat_join(fn) or al <= key_pos[0] or ar <= key_pos[1]:
+        return None
+    call = fn.join if hasattr(fn, "join") else fn
+    left = E.RowProxy([E.FieldRef("key") if j == key_pos[0] else E.var(j) for j in range(al)])
+    right = E.RowProxy([E.FieldRef("key") if j == key_pos[1] else E.var(_JOIN_RIGHT + j)
+                        for j in range(ar)])
+    try:
+        res = call(left, right)
+    except Exception:  # noqa: BLE001 -- anything that does not trace keeps the host operators
+        return None
+    if not isinstance(res, tuple) or isinstance(res, E.RowProxy) or not res:
+        return None
+    layout, vals = [], [None, None]
+    for f in res:
+        if isinstance(f, E.FieldRef):
+            layout.append("k")
+        elif isinstance(f, E.Expr) and f.op == "var":
+            side, j = divmod(int(f.value), _JOIN_RIGHT)
+            if vals[side] not in (None, j):
+                return None
+            vals[side] = j
+            layout.append("lr"[side])
+        else:
+            return None
+    if vals[0] is None or vals[1] is None:
+        return None
+    return tuple(layout), vals[0], vals[1]
+
+
+def _lower_join(env, t, meta) -> None:
+    """``a.join(b).where(p).equal_to(q).window(w).apply(fn)`` -> NativeJoinOp when both keys are
+    field positions, `w` is a tumbling / sliding event-time assigner with the default trigger,
+    no evictor, lateness 0 and no late tag, one rank runs the job and `fn` traces to a
+    projection (trace_join_projection). Anything else -- and every co-group -- keeps the host
+    plan: tagged union -> keyed window -> the co-group function."""
+    from ..runtime.native_ops import NativeJoinOp
+
+    ws = meta["stream"]
+    a = ws.assigner
+    kp = meta["key_pos"]
+    comm = getattr(env, "_comm", None)
+    world = comm.world if comm is not None else getattr(env, "world", 1)
+    if meta.get("co_group") or kp[0] is None or kp[1] is None or world > 1:
+        return
+    if type(a) not in (W.TumblingEventTimeWindows, W.SlidingEventTimeWindows):
+        return
+    if ws._trigger is not None or ws._evictor is not None or ws._lateness or \
+            ws._late_tag is not None:
+        return
+    fn = meta["fn"]
+    shape, ok = None, (set(), set())
+    for side in (0, 1):
+        for ar in range(2, 9):
+            tr = trace_join_projection(fn, kp, ar if side == 0 else 8, 8 if side == 0 else ar)
+            if tr is None:
+                continue
+            if shape is None:
+                shape = tr
+            if tr == shape:
+                ok[side].add(ar)
+    if shape is None or not ok[0] or not ok[1]:
+        return
+    layout, lval, rval = shape
+    fallback = t.factory
+    device = env.config.device
+    assigner = a
+
+    def factory():
+        return NativeJoinOp(key_pos=kp, val_pos=(lval, rval), layout=layout,
+                            ok_arities=(frozenset(ok[0]), frozenset(ok[1])), assigner=assigner,
+                            device=device, fallback_factory=fallback)
+
+    t.factory = factory
+    t.meta = dict(t.meta, native=True)
+    meta["columnar"]["on"] = True  # the tag operators let column batches through as they are

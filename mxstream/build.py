@@ -26,10 +26,10 @@ ARCH = os.environ.get("MXS_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["kernels_hip.hip", "sort_hip.hip", "parse_hip.hip", "vector_hip.hip",
                "check_hip.hip", "rolling_hist_hip.hip", "ingest_hip.hip", "listwin_hip.hip",
-               "format_hip.hip", "exchange_hip.hip"]
+               "format_hip.hip", "exchange_hip.hip", "join_hip.hip"]
 CXX_SOURCES = ["kernels_cpu.cpp", "ingest_cpu.cpp", "runtime.cpp", "sessions.cpp", "vector_cpu.cpp",
                "vector_bindings.cpp", "trace.cpp", "check_cpu.cpp", "reader.cpp", "format.cpp", "listwin_cpu.cpp",
-               "listwin_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
+               "listwin_bindings.cpp", "join_cpu.cpp", "join_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
                "window_step.cpp", "window_step_bindings.cpp", "bindings.cpp"]
 # roctx ranges (csrc/trace.cpp) come from the ROCm profiler SDK's marker library.
 LINK_LIBS = ["-L/opt/rocm/lib", "-lrocprofiler-sdk-roctx", "-Wl,-rpath,/opt/rocm/lib"]
@@ -117,7 +117,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     return out
 
 
-SANITIZE_SOURCES = ["kernels_cpu.cpp", "vector_cpu.cpp", "tests/sanitize_main.cpp"]
+SANITIZE_SOURCES = ["kernels_cpu.cpp", "vector_cpu.cpp", "join_cpu.cpp", "tests/sanitize_main.cpp"]
 SANITIZE_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                   "-fno-sanitize-recover=all"]
 

@@ -817,6 +817,87 @@ def config8(steps: int, warmup: int, batch: int = 1 << 22, keys: int = 100_000,
     return res
 
 
+def config13(steps: int, warmup: int, batch: int | None = None, keys: int = 100_000,
+             size: int = 1_000, slide: int | None = None, zipf: float = 0.0,
+             device: str = "cuda") -> dict:
+    """Keyed window join at scale: two device-generated streams (two stream ids of gen_events)
+    of `batch` events per side and step feed KeyedJoinWindowOperator directly; every firing
+    matches the sides' key segments, scans the pair counts and expands every pair into three
+    int64 columns on the device (24 B per pair, nothing copied to the host).
+
+    Defaults: 100,000 keys, 2**21 events per side and 1 s step, tumbling 1 s windows -- a firing
+    holds about 21 events per key and side, so about 100,000 x 21 x 21 = 4.4e7 pairs. With
+    `zipf` > 0 a few keys take most of the events (exponent 1.2: key 0 is the hottest), and a
+    key's pair count grows with the square of its share: the default batch is then 2**15 per side
+    and step, which gives a firing of the same order (about 3.6e7 pairs, most of them of the
+    hottest keys).
+    Also timed in the same call: a device fill of one firing's output bytes."""
+    from ..runtime.join_window_operator import KeyedJoinWindowOperator
+
+    dev = torch.device(device)
+    if batch is None:
+        batch = (1 << 15) if zipf > 0 else (1 << 21)
+    step_ms, disorder = 1_000, 200
+    op = KeyedJoinWindowOperator(size=size, slide=slide, device=dev)
+    cols = [[torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3)] for _ in (0, 1)]
+    t0_event = 1_566_957_600_000
+    state = {"i": 0}
+    lat: list[float] = []
+    firings = {"n": 0, "pairs": 0}
+
+    def step():
+        i = state["i"]
+        t_in = time.perf_counter()
+        for sd, (kt, tt, vt) in enumerate(cols):
+            K.gen_events(kt, tt, vt, seed=13, stream_id=sd, idx0=i * batch, nkeys=keys,
+                         ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=disorder,
+                         val_lo=0, val_span=10_000, val_f64=True, zipf=zipf)
+            op.process(sd, kt, tt, vt)
+        fired = op.advance_watermark(t0_event + (i + 1) * step_ms - disorder - 1)
+        n = sum(int(r[2].numel()) for r in fired)
+        if fired:
+            _sync(dev)  # the expand of this step, not the next step's first readback, ends it
+            lat.append((time.perf_counter() - t_in) * 1e3)
+            firings["n"] += len({r[0] for r in fired})
+            firings["pairs"] += n
+        state["i"] = i + 1
+        return n
+
+    for _ in range(warmup):
+        step()
+    _sync(dev)
+    lat.clear()
+    firings.update(n=0, pairs=0)
+    t0 = time.perf_counter()
+    pairs = 0
+    for _ in range(steps):
+        pairs += step()
+    _sync(dev)
+    dt = time.perf_counter() - t0
+    per_firing = firings["pairs"] // max(1, firings["n"])
+    res = {"config": 13, "metric": "events/sec (keyed window join, both sides)",
+           "value": 2 * batch * steps / dt, "unit": "events/s", "pairs_per_s": pairs / dt,
+           "ms_per_step": dt / steps * 1e3,
+           "p50_fire_step_ms": statistics.median(lat) if lat else None,
+           "pairs": pairs, "firings": firings["n"], "pairs_per_firing": per_firing,
+           "expand_bytes": 24 * pairs, "late_dropped": op.metrics.num_late_records_dropped,
+           "keys": keys, "events_per_side_and_step": batch, "size_ms": size,
+           "slide_ms": slide or size, "zipf": zipf, "device": str(dev)}
+    if per_firing:
+        # The same number of bytes written by a plain device fill (the streaming-store yardstick).
+        buf = torch.empty(3 * per_firing, dtype=torch.int64, device=dev)
+        buf.fill_(1)
+        _sync(dev)
+        t1 = time.perf_counter()
+        for _ in range(5):
+            buf.fill_(2)
+        _sync(dev)
+        fill_ms = (time.perf_counter() - t1) / 5 * 1e3
+        res["fill_ms_per_firing_bytes"] = fill_ms
+        res["fill_GBps"] = 24 * per_firing / fill_ms / 1e6
+    return res
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1099,13 +1180,14 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
     ap.add_argument("--dim", type=int, default=32, help="config 6: metric vector width")
     ap.add_argument("--valu", action="store_true", help="config 6: VALU instead of MFMA reduce")
-    ap.add_argument("--zipf", type=float, default=0.0, help="config 6: power-law key skew")
+    ap.add_argument("--zipf", type=float, default=0.0,
+                    help="config 6 / 13: power-law key skew (13: 1.2 is the hot-key case)")
     ap.add_argument("--host-fold", action="store_true",
                     help="config 5: fold records of spilled keys in host DRAM (no promotion to HBM)")
     ap.add_argument("--spill", action="store_true",
@@ -1118,7 +1200,10 @@ def main(argv=None) -> int:
                     help="config 5: fraction of events for spilled (long idle) keys")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--batch", type=int, default=None,
+                    help="events per step; config 13: per side and step (default 2**21, and "
+                         "2**15 with --zipf, where a hot key's pairs grow with the square of "
+                         "its events)")
     ap.add_argument("--lines", type=int, default=None, help="config 7: lines in the file")
     ap.add_argument("--profile", action="store_true", help="config 7: cProfile the job")
     ap.add_argument("--device", default="cuda")
@@ -1127,14 +1212,16 @@ def main(argv=None) -> int:
                     help="configs 2/4: hashed keyed state instead of dictionary-id slots")
     ap.add_argument("--sort-path", action="store_true",
                     help="config 2: the radix-sort rolling path instead of the sort-free one")
-    ap.add_argument("--keys", type=int, default=None, help="config 2: key space (default 10k)")
+    ap.add_argument("--keys", type=int, default=None, help="config 2: key space (default 10k); config 13: 100k")
     ap.add_argument("--size", type=int, default=None,
                     help="config 11: count-window size (default 100); config 12: the tumbling "
-                         "countWindow(size) instead of the rolling aggregate")
+                         "countWindow(size) instead of the rolling aggregate; config 13: window "
+                         "size in ms (default 1000)")
     ap.add_argument("--by", choices=["max", "min"], default=None,
                     help="config 12: the arg-select scan of maxBy / minBy instead of the plain max")
     ap.add_argument("--slide", type=int, default=None,
-                    help="config 11: count-window slide (omitted: the tumbling countWindow(size))")
+                    help="config 11: count-window slide (omitted: the tumbling countWindow(size)); "
+                         "config 13: window slide in ms (omitted: tumbling)")
     ap.add_argument("--latency-fire", type=int, default=0,
                     help="config 4: fire right away when at most this many windows are due "
                          "(latency-bounded mode; 0 = pipelined firing)")
@@ -1181,6 +1268,9 @@ def main(argv=None) -> int:
     elif a.config == 12:
         r = config12(a.steps, a.warmup, a.batch or (1 << 24), keys=a.keys or 10_000,
                      size=a.size or 0, by=a.by, device=a.device)
+    elif a.config == 13:
+        r = config13(a.steps, a.warmup, a.batch, keys=a.keys or 100_000, size=a.size or 1_000,
+                     slide=a.slide, zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

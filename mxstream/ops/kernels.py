@@ -681,3 +681,100 @@ def segment_distinct(heads: torch.Tensor, ord_bits: torch.Tensor) -> torch.Tenso
     out, meta = segment_distinct_launch(heads, heads.numel(), ord_bits.numel(), ord_bits)
     segment_distinct_check(meta)
     return out
+
+
+# ---- keyed window joins (csrc/mxs_join.h) ------------------------------------------------------
+
+@dataclass
+class JoinPlan:
+    """A matched and scanned pair of gathered firings (``join_plan``): what ``join_expand``
+    needs to write any range of the firing's P pairs."""
+    lkeys: torch.Tensor
+    lheads: torch.Tensor
+    ltotal: int
+    rkeys: torch.Tensor
+    rheads: torch.Tensor
+    rtotal: int
+    match: torch.Tensor     # int64 [kL]: the right segment of each left segment, or -1
+    cnt: torch.Tensor       # int64 [kL]: nL * nR
+    pair_off: torch.Tensor  # int64 [kL + 1]: exclusive scan of cnt, pair_off[kL] = P
+    plan: torch.Tensor      # int64 [JOIN_PLAN_COLS * (kL + 1)]: the matched segments, compacted
+    pairs: int              # P
+    matched: int            # m
+
+
+def _join_side(keys, heads, total: int, name: str, dev, validate: bool):
+    _check(keys, torch.int64, 0, name + "keys", dev)
+    _check(heads, torch.int64, keys.numel(), name + "heads", dev)
+    if keys.dim() != 1 or heads.dim() != 1 or heads.numel() != keys.numel():
+        raise ValueError(f"{name}keys / {name}heads: one start per key segment expected")
+    if total < 0 or (keys.numel() == 0) != (total == 0):
+        raise ValueError(f"{name}total: {total} elements in {keys.numel()} segments")
+    if validate and keys.numel():
+        if int(heads[0]) != 0 or int(heads[-1]) >= total or \
+                (heads.numel() > 1 and bool((heads[1:] <= heads[:-1]).any())):
+            raise ValueError(f"{name}heads: segment starts must ascend from 0 below {name}total")
+        if keys.numel() > 1 and bool((keys[1:] <= keys[:-1]).any()):
+            raise ValueError(f"{name}keys: key ids must ascend strictly")
+
+
+def join_plan(lkeys: torch.Tensor, lheads: torch.Tensor, ltotal: int, rkeys: torch.Tensor,
+              rheads: torch.Tensor, rtotal: int, *, validate: bool = True) -> JoinPlan:
+    """Match the key segments of two gathered firings and scan the pair counts: every left
+    segment's right segment (binary search in `rkeys`) and nL * nR, the exclusive 64-bit scan
+    ``pair_off`` and the compacted plan of the matched segments. One readback (P, m, the error
+    word); a firing of 2**62 pairs or more raises OverflowError."""
+    dev = lkeys.device
+    ltotal, rtotal = int(ltotal), int(rtotal)
+    _join_side(lkeys, lheads, ltotal, "l", dev, validate)
+    _join_side(rkeys, rheads, rtotal, "r", dev, validate)
+    m = load()
+    kl, kr = lkeys.numel(), rkeys.numel()
+    cuda = _is_gpu(lkeys)
+    st = _stream(lkeys) if cuda else 0
+    match = torch.empty(kl, dtype=torch.int64, device=dev)
+    cnt = torch.empty(kl, dtype=torch.int64, device=dev)
+    pair_off = torch.empty(kl + 1, dtype=torch.int64, device=dev)
+    plan = torch.empty(m.JOIN_PLAN_COLS * (kl + 1), dtype=torch.int64, device=dev)
+    meta = torch.zeros(m.JOIN_META, dtype=torch.int64, device=dev)
+    scratch = torch.empty(max(16, m.join_scan_scratch_bytes(kl)), dtype=torch.uint8, device=dev)
+    sides = (lkeys.data_ptr(), lheads.data_ptr(), kl, ltotal,
+             rkeys.data_ptr(), rheads.data_ptr(), kr, rtotal)
+    m.join_match(cuda, *sides, match.data_ptr(), cnt.data_ptr(), st)
+    m.join_scan(cuda, *sides, match.data_ptr(), cnt.data_ptr(), scratch.data_ptr(),
+                pair_off.data_ptr(), plan.data_ptr(), meta.data_ptr(), st)
+    pairs, matched, err, _ = meta.tolist()
+    if err or pairs >= m.JOIN_MAX_PAIRS:
+        raise OverflowError("window join: a firing of 2**62 pairs or more")
+    return JoinPlan(lkeys, lheads, ltotal, rkeys, rheads, rtotal, match, cnt, pair_off, plan,
+                    pairs, matched)
+
+
+def join_expand(jp: JoinPlan, lord: torch.Tensor, rord: torch.Tensor, p0: int, p1: int):
+    """Pairs [p0, p1) of the planned firing as three int64 columns of p1 - p0 rows: the key id,
+    the left value's and the right value's f64 bit patterns (`lord` / `rord`: the sides' order
+    bits). Position p of a matched key is left-major: a = q / nR, b = q % nR."""
+    dev = jp.lkeys.device
+    p0, p1 = int(p0), int(p1)
+    _check(lord, torch.int64, jp.ltotal, "lord", dev)
+    _check(rord, torch.int64, jp.rtotal, "rord", dev)
+    if not 0 <= p0 <= p1 <= jp.pairs:
+        raise ValueError(f"pair range [{p0}, {p1}) outside [0, {jp.pairs})")
+    n = p1 - p0
+    out = torch.empty((3, n), dtype=torch.int64, device=dev)
+    if n == 0:
+        return out[0], out[1], out[2]
+    if n % 2:  # every column starts 16-byte aligned (the kernel's paired stores)
+        out = torch.empty((3, n + 1), dtype=torch.int64, device=dev)[:, :n]
+    ok, ol, orr = out[0], out[1], out[2]
+    m = load()
+    if _is_gpu(lord):
+        m.gpu_join_expand(jp.plan.data_ptr(), jp.lkeys.numel(), jp.matched, jp.pairs,
+                          lord.data_ptr(), rord.data_ptr(), p0, p1, ok.data_ptr(), ol.data_ptr(),
+                          orr.data_ptr(), _stream(lord))
+    else:
+        m.cpu_join_expand(jp.lkeys.data_ptr(), jp.lheads.data_ptr(), jp.lkeys.numel(), jp.ltotal,
+                          jp.rkeys.data_ptr(), jp.rheads.data_ptr(), jp.rkeys.numel(), jp.rtotal,
+                          jp.match.data_ptr(), jp.pair_off.data_ptr(), lord.data_ptr(),
+                          rord.data_ptr(), p0, p1, ok.data_ptr(), ol.data_ptr(), orr.data_ptr())
+    return ok, ol, orr

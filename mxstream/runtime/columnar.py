@@ -64,6 +64,7 @@ class ColumnBatch:
     sub: np.ndarray | None = None        # subtask per row
     scalar: bool = False                 # one column of bare values (not Tuple1 rows)
     _cache: dict = field(default_factory=dict)
+    side: int | None = None              # join input (TagSideOp): every row is of this side
 
     def field_value(self, j: int, i: int):
         v = self.cols[j][i]
@@ -94,8 +95,9 @@ class ColumnBatch:
         ts = self.ts.tolist() if self.ts is not None else [LONG_MIN] * self.n
         sub = self.sub.tolist() if self.sub is not None else [0] * self.n
         if self.scalar:
-            return [Rec(v, t, s) for v, t, s in zip(cols[0], ts, sub)]
-        return [Rec(Tuple(row), t, s) for row, t, s in zip(zip(*cols), ts, sub)]
+            return _tag_recs([Rec(v, t, s) for v, t, s in zip(cols[0], ts, sub)], self.side)
+        return _tag_recs([Rec(Tuple(row), t, s) for row, t, s in zip(zip(*cols), ts, sub)],
+                         self.side)
 
     def take(self, mask: np.ndarray) -> "ColumnBatch":
         idx = np.nonzero(mask)[0]
@@ -161,10 +163,17 @@ class DeviceColumnBatch(ColumnBatch):
         return self.host().value(i)
 
     def to_recs(self) -> list[Rec]:
-        return self.host().to_recs()
+        return _tag_recs(self.host().to_recs(), self.side)
 
     def take(self, mask: np.ndarray) -> ColumnBatch:
         return self.host().take(mask)
+
+
+def _tag_recs(recs: list, side) -> list:
+    """Rows of a join input as the tagged records of the host plan: (side, value)."""
+    if side is None:
+        return recs
+    return [Rec(Tuple((side, r.value)), r.ts, r.subtask) for r in recs]
 
 
 def _to_host(cols: list) -> list:
@@ -242,6 +251,36 @@ class PassThroughOp(Operator):
 
     def process(self, items):
         return items
+
+
+class TagSideOp(Operator):
+    """Tags one input of a window join / co-group with its side (0 = left, 1 = right) before the
+    union, as Flink's JoinedStreams maps both inputs into a tagged union. A record's value
+    becomes the Flink tuple (side, value): typed state, so the keyed exchange and checkpoints
+    carry it as it is. With ``columnar`` (set by the planner when the join runs natively) a
+    column batch stays a column batch and carries the side as an attribute, not per row;
+    wherever it is expanded after all, its rows come out as the same tagged records."""
+
+    name = "Join(tag)"
+
+    def __init__(self, side: int, columnar: bool = False):
+        self.tag = int(side)
+        self.accepts_columns = bool(columnar)
+
+    def process(self, items):
+        import copy
+
+        out = []
+        for it in items:
+            if isinstance(it, WM):
+                out.append(it)
+            elif isinstance(it, ColumnBatch):
+                cb = copy.copy(it)
+                cb.side = self.tag
+                out.append(cb)
+            else:
+                out.append(Rec(Tuple((self.tag, it.value)), it.ts, it.subtask))
+        return out
 
 
 class TextParseOp(Operator):

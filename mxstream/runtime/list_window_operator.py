@@ -315,11 +315,14 @@ class KeyedListWindowOperator:
                 out.append(r)
         return out
 
-    def _fire_window(self, s: int, only_keys: torch.Tensor | None = None) -> list:
+    def _window_route(self, s: int):
+        """How the window starting at `s` is gathered: ("ranked" | "dense" | "mapped", args of
+        that path), or None when the window holds no element. Ranked panes place every element
+        without atomics, dense key ranges go through the counting sort, anything else through
+        dense ids first."""
         slots = self._window_panes(s)
         if not slots:
-            return []
-        self.metrics.num_fires += 1
+            return None
         total = sum(self.fill[r] for r in slots)
         kmin = min(self.krange[r][0] for r in slots)
         kmax = max(self.krange[r][1] for r in slots)
@@ -330,11 +333,27 @@ class KeyedListWindowOperator:
             rhi = max(self.kbase[r] + self.kcnt[r].numel() for r in slots)
             ranked = rhi - rlo <= _MAX_DENSE
         if ranked:
-            keys_out, med = self._fire_ranked(slots, rlo, rhi - rlo, total)
-        elif kmin >= 0 and kmax - kmin < _MAX_DENSE and len(slots) <= 64:
-            keys_out, med = self._fire_dense(slots, kmin, kmax - kmin + 1, total)
-        else:
-            keys_out, med = self._fire_mapped(slots)
+            return "ranked", (slots, rlo, rhi - rlo, total)
+        if kmin >= 0 and kmax - kmin < _MAX_DENSE and len(slots) <= 64:
+            return "dense", (slots, kmin, kmax - kmin + 1, total)
+        return "mapped", (slots,)
+
+    def _gather_window(self, s: int):
+        """The window starting at `s` gathered into key segments, without the window function:
+        (hkeys, heads, k, total, ordv) -- the k non-empty keys ascending, their segment starts in
+        `ordv` (the window's `total` values as f64 order bits) -- or None when the window holds
+        no element."""
+        route = self._window_route(s)
+        if route is None:
+            return None
+        return getattr(self, "_gather_" + route[0])(*route[1])
+
+    def _fire_window(self, s: int, only_keys: torch.Tensor | None = None) -> list:
+        route = self._window_route(s)
+        if route is None:
+            return []
+        self.metrics.num_fires += 1
+        keys_out, med = getattr(self, "_fire_" + route[0])(*route[1])
         if only_keys is not None:
             sel = torch.isin(keys_out, only_keys.to(keys_out.device))
             keys_out, med = keys_out[sel], med[..., sel]  # the key axis is the last one
@@ -370,10 +389,10 @@ class KeyedListWindowOperator:
             m.cpu_segment_quantile_select(*args, self.ppm, res.data_ptr())
         return res
 
-    def _fire_ranked(self, slots, kmin: int, nk: int, total: int):
-        """Ranked firing: per-key totals and per-pane prefixes from the panes' counts, the
+    def _gather_ranked(self, slots, kmin: int, nk: int, total: int):
+        """Ranked gather: per-key totals and per-pane prefixes from the panes' counts, the
         order-preserving scan, then every element placed at segment start + prefix + rank (no
-        atomics), then the per-segment selection."""
+        atomics)."""
         m, st, dev = self._m, self._stream(), self.device
         panes = [(self.kbuf[r].data_ptr(), self.vbuf[r].data_ptr(), self.rbuf[r].data_ptr(),
                   self.kcnt[r].data_ptr(), self.kbase[r], self.kcnt[r].numel(), self.fill[r])
@@ -392,9 +411,9 @@ class KeyedListWindowOperator:
         m.lw_rank_scatter(self.cuda, panes, kmin, nk, offs.data_ptr(), pre.data_ptr(),
                           ordv.data_ptr(), st)
         k = int(nh.item())
-        return hkeys[:k], self._select(heads, k, total, ordv)
+        return hkeys[:k], heads, k, total, ordv
 
-    def _fire_dense(self, slots, kmin: int, nk: int, total: int):
+    def _gather_dense(self, slots, kmin: int, nk: int, total: int):
         m, st, dev = self._m, self._stream(), self.device
         panes = [(self.kbuf[r].data_ptr(), self.vbuf[r].data_ptr(), self.fill[r]) for r in slots]
         counts = torch.zeros(nk, dtype=torch.int32, device=dev)
@@ -410,10 +429,10 @@ class KeyedListWindowOperator:
         ordv = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
         m.lw_key_scatter(self.cuda, panes, kmin, cursor.data_ptr(), ordv.data_ptr(), st)
         k = int(nh.item())
-        return hkeys[:k], self._select(heads, k, total, ordv)
+        return hkeys[:k], heads, k, total, ordv
 
-    def _fire_mapped(self, slots):
-        """Keys outside a dense id range: dense ids by torch.unique, then the same firing."""
+    def _gather_mapped(self, slots):
+        """Keys outside a dense id range: dense ids by torch.unique, then the same gather."""
         keys = torch.cat([self.kbuf[r][:self.fill[r]] for r in slots])
         vals = torch.cat([self.vbuf[r][:self.fill[r]] for r in slots])
         uniq, ids = torch.unique(keys, return_inverse=True)
@@ -434,7 +453,20 @@ class KeyedListWindowOperator:
         cursor = offs[:nk].clone()
         ordv = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         m.lw_key_scatter(self.cuda, panes, 0, cursor.data_ptr(), ordv.data_ptr(), st)
-        return uniq, self._select(heads, nk, n, ordv)
+        return uniq, heads, nk, n, ordv
+
+    # The three firing paths: their gather, then the window function over the segments.
+    def _fire_ranked(self, slots, kmin: int, nk: int, total: int):
+        hkeys, heads, k, total, ordv = self._gather_ranked(slots, kmin, nk, total)
+        return hkeys, self._select(heads, k, total, ordv)
+
+    def _fire_dense(self, slots, kmin: int, nk: int, total: int):
+        hkeys, heads, k, total, ordv = self._gather_dense(slots, kmin, nk, total)
+        return hkeys, self._select(heads, k, total, ordv)
+
+    def _fire_mapped(self, slots):
+        hkeys, heads, k, total, ordv = self._gather_mapped(slots)
+        return hkeys, self._select(heads, k, total, ordv)
 
     # ---- checkpoints ------------------------------------------------------------------------
     def snapshot_state(self):

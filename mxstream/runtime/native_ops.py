@@ -2010,3 +2010,319 @@ class NativeVectorWindowOp(NativeWindowOp):
             self._vjh_t = torch.from_numpy(self.dict.jhash_table())
         self._build([0.0] * eng["vlen"])
         self.op.restore_state(eng["columns"], eng["meta"])
+
+
+class NativeJoinOp(Operator):
+    """``a.join(b).where(p).equal_to(q).window(tumbling | sliding event time).apply(fn)`` on the
+    device join operator (runtime/join_window_operator.py) when `fn` is a projection: a tuple of
+    the key and one value field of each side (planner._lower_join). Input is the tagged union of
+    the host plan (records ``(side, value)``, or column batches that carry their side); each
+    side keeps its (key id, timestamp, value bits) rows in a pane arena of its own, and a firing
+    matches the key segments and expands every matched key's pairs on the device.
+
+    One dictionary, owned by the operator, holds both sides' string keys: the ids of every
+    upstream dictionary are translated through a table that grows with that dictionary (a name is
+    interned once, a device batch is translated on the device), so nothing is ever interned into
+    a parser's dictionary. Each side has a value kind of
+    its own: doubles, or integers carried as the bit pattern of ``float(x)`` (exact for
+    |x| <= 2**53) that come back as longs. Mixed key types, a non-numeric value, an integer
+    beyond 2**53 or a wrong arity switch to the host operator before native state exists and
+    raise afterwards. Output: one host ColumnBatch per fired chunk in `fn`'s layout."""
+
+    name = "Window(native join)"
+    accepts_columns = True
+    _INT_EXACT = 1 << 53
+
+    def __init__(self, *, key_pos, val_pos, layout, ok_arities, assigner, device: str,
+                 fallback_factory, pair_chunk: int = 1 << 24):
+        self.key_positions, self.val_positions = tuple(key_pos), tuple(val_pos)
+        self.layout = tuple(layout)            # "k" | "l" | "r" per output field
+        self.ok_arities = tuple(ok_arities)    # per side
+        self.assigner = assigner
+        self.device = device
+        self.fallback_factory = fallback_factory
+        self.pair_chunk = pair_chunk
+        self.op = None
+        self.fallback = None
+        self.wm = LONG_MIN
+        self.pending: list = []
+        self._idmaps: dict = {}                # id(upstream dictionary) -> (it, its ids -> ours)
+        self.is_float = [None, None]
+        self._subs: dict = {}
+        self._late = 0
+
+    @property
+    def num_late_records_dropped(self) -> int:
+        if self.fallback is not None:
+            return self.fallback.num_late_records_dropped
+        return self._late
+
+    def open(self, ctx):
+        super().open(ctx)
+        from ..ops.native import load
+
+        self.dict = load().StringDict()
+        self.str_keys = None
+        comm = getattr(ctx, "comm", None)
+        if comm is not None and comm.world > 1:
+            self._to_fallback()  # several ranks: host operators behind the keyed exchange
+
+    _subtasks = NativeWindowOp._subtasks
+    _key_id = NativeWindowOp._key_id
+
+    def _to_fallback(self):
+        self.fallback = self.fallback_factory()
+        self.fallback.open(self.ctx)
+        if self.wm > LONG_MIN:
+            # no record has been kept yet, but the host operator must know the watermark that
+            # later records are late against (nothing fires: its output is that watermark again)
+            self.fallback.process([WM(self.wm)])
+
+    def _own_ids(self, strings, need: int) -> np.ndarray:
+        """Table from the ids of an upstream dictionary to this operator's, covering ids < need."""
+        _, tab = self._idmaps.get(id(strings), (None, np.zeros(0, dtype=np.int64)))
+        if tab.size < need:
+            names = strings.strings()
+            tab = np.concatenate([tab, np.array([self.dict.intern(x) for x in names[tab.size:]],
+                                                dtype=np.int64)])
+            self._idmaps[id(strings)] = (strings, tab)  # (keeps `strings` alive: id() stays its)
+        if tab.size < need:
+            raise TypeError("key id outside its dictionary")
+        return tab
+
+    def _batch_keys(self, cb: ColumnBatch, kp: int):
+        """Key ids of a column batch (numpy, or a device tensor for a device batch)."""
+        kk = cb.kinds[kp]
+        device = isinstance(cb, DeviceColumnBatch)
+        col = cb.cols[kp][:cb.n]
+        if kk == FK_DOUBLE:
+            raise TypeError("double keys on the native path")
+        if self.str_keys is not None and self.str_keys != (kk == FK_STR):
+            raise TypeError("mixed key types")
+        self.str_keys = kk == FK_STR
+        if not cb.n:
+            return col.to(torch.int64) if device else col.astype(np.int64)
+        lo, hi = (torch.stack([col.min(), col.max()]).tolist() if device
+                  else (int(col.min()), int(col.max())))
+        if lo < 0 or hi >= (1 << 63) - 2:
+            raise TypeError("negative / reserved keys on the native path")
+        if kk != FK_STR:
+            return col.to(torch.int64) if device else col.astype(np.int64, copy=False)
+        tab = self._own_ids(cb.strings, hi + 1)
+        if device:
+            return torch.from_numpy(tab).to(col.device)[col.to(torch.int64)]
+        return tab[col]
+
+    def _build(self) -> None:
+        from .join_window_operator import KeyedJoinWindowOperator
+
+        a = self.assigner
+        self.op = KeyedJoinWindowOperator(size=a.size, slide=a.slide, offset=a.offset,
+                                          device=torch.device(self.device),
+                                          pair_chunk=self.pair_chunk)
+
+    # -- input: one side's pending items as (key ids, timestamps, value bits) -------------------
+    def _kind(self, side: int, is_float: bool, kinds: list) -> None:
+        if kinds[side] is None:
+            kinds[side] = is_float
+        elif kinds[side] != is_float:
+            raise TypeError("mixed value types")
+
+    def _int_bits(self, col: np.ndarray) -> np.ndarray:
+        if col.size and (int(col.min()) < -self._INT_EXACT or int(col.max()) > self._INT_EXACT):
+            raise TypeError("mixed value types")  # not every value is a double: host operator
+        return col.astype(np.float64).view(np.int64)
+
+    def _recs_columns(self, side: int, recs: list, kinds: list):
+        kp, vp = self.key_positions[side], self.val_positions[side]
+        n = len(recs)
+        kid = np.empty(n, dtype=np.int64)
+        tsa = np.empty(n, dtype=np.int64)
+        v0 = recs[0].value[1]
+        if not isinstance(v0, tuple) or len(v0) <= vp or isinstance(v0[vp], bool) \
+                or not isinstance(v0[vp], (int, float)):
+            raise TypeError("unsupported value")
+        is_float = isinstance(v0[vp], float)
+        self._kind(side, is_float, kinds)
+        vv = np.empty(n, dtype=np.float64 if is_float else np.int64)
+        for i, r in enumerate(recs):
+            v = r.value[1]
+            if not isinstance(v, tuple) or len(v) not in self.ok_arities[side]:
+                raise TypeError("wrong arity")
+            kid[i] = self._key_id(v[kp])
+            tsa[i] = r.ts
+            x = v[vp]
+            if isinstance(x, bool) or not isinstance(x, (int, float)) \
+                    or isinstance(x, float) != is_float:
+                raise TypeError("mixed value types")
+            if not is_float and not -self._INT_EXACT <= x <= self._INT_EXACT:
+                raise TypeError("mixed value types")
+            vv[i] = x
+        return kid, tsa, vv.view(np.int64) if is_float else self._int_bits(vv)
+
+    def _batch_columns(self, side: int, cb: ColumnBatch, kinds: list):
+        kp, vp = self.key_positions[side], self.val_positions[side]
+        if isinstance(cb, DeviceColumnBatch) and (self.op is None
+                                                  or self.op.device.type != "cuda"):
+            cb = cb.host()  # no engine on the batch's device (yet): host columns
+        if len(cb.kinds) not in self.ok_arities[side] or cb.kinds[vp] == FK_STR or cb.scalar:
+            raise TypeError("value column not numeric")
+        is_float = cb.kinds[vp] == FK_DOUBLE
+        self._kind(side, is_float, kinds)
+        n = cb.n
+        if isinstance(cb, DeviceColumnBatch):
+            kid = self._batch_keys(cb, kp)
+            col = cb.cols[vp][:n]
+            if is_float:
+                bits = col.view(torch.int64)
+            else:
+                col = col.to(torch.int64)
+                if n:
+                    lo, hi = torch.stack([col.min(), col.max()]).tolist()
+                    if lo < -self._INT_EXACT or hi > self._INT_EXACT:
+                        raise TypeError("mixed value types")
+                bits = col.to(torch.float64).view(torch.int64)
+            ts = cb.ts[:n] if cb.ts is not None else torch.full(
+                (n,), LONG_MIN, dtype=torch.int64, device=col.device)
+            return kid, ts, bits
+        kid = self._batch_keys(cb, kp)
+        col = cb.cols[vp]
+        bits = (np.ascontiguousarray(col, dtype=np.float64).view(np.int64) if is_float
+                else self._int_bits(col.astype(np.int64, copy=False)))
+        ts = cb.ts if cb.ts is not None else np.full(n, LONG_MIN, dtype=np.int64)
+        return kid, np.ascontiguousarray(ts, dtype=np.int64), bits
+
+    @staticmethod
+    def _side_of(it) -> int:
+        side = it.side if isinstance(it, ColumnBatch) else (
+            it.value[0] if isinstance(it.value, tuple) and len(it.value) == 2 else None)
+        if side not in (0, 1) or isinstance(side, bool):
+            raise TypeError("join input without a side")
+        return side
+
+    def _flush(self) -> list:
+        items, self.pending = self.pending, []
+        if not items:
+            return []
+        kinds = list(self.is_float)
+        try:
+            parts = []  # (side, kid, ts, bits) runs in arrival order
+            run_side, run = None, []
+            for it in items + [None]:
+                s = None if it is None else self._side_of(it)
+                batch = isinstance(it, ColumnBatch)
+                if run and (s != run_side or batch):
+                    parts.append((run_side,) + self._recs_columns(run_side, run, kinds))
+                    run = []
+                if it is None:
+                    break
+                if batch:
+                    if it.n:
+                        parts.append((s,) + self._batch_columns(s, it, kinds))
+                else:
+                    run_side = s
+                    run.append(it)
+        except TypeError:
+            # Unsupported data for the native path: the exact host operator, while no native
+            # state exists yet.
+            if self.op is not None:
+                raise
+            self._to_fallback()
+            return self.fallback.process(expand_columns(items))
+        self.is_float = kinds
+        if self.op is None:
+            self._build()
+        dev = self.op.device
+        to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray)  # noqa: E731
+                            else x).to(dev)
+        for side in (0, 1):
+            mine = [p for p in parts if p[0] == side]
+            if not mine:
+                continue
+            cols = [torch.cat([to_dev(p[j]) for p in mine]) for j in (1, 2, 3)]
+            self.op.process(side, *cols)
+        self._late = self.op.metrics.num_late_records_dropped
+        return []
+
+    # -- output ---------------------------------------------------------------------------------
+    def _emit(self, fired) -> list:
+        out = []
+        for _s, end, keys, lv, rv in fired:
+            keys, lv, rv = (x.cpu().numpy() for x in (keys, lv, rv))
+            cols, kinds = [], []
+            for f in self.layout:
+                if f == "k":
+                    cols.append(keys)
+                    kinds.append(FK_STR if self.str_keys else FK_LONG)
+                else:
+                    bits, is_float = (lv, self.is_float[0]) if f == "l" else (rv, self.is_float[1])
+                    vals = np.ascontiguousarray(bits).view(np.float64)
+                    cols.append(vals if is_float else vals.astype(np.int64))
+                    kinds.append(FK_DOUBLE if is_float else FK_LONG)
+            n = int(keys.size)
+            out.append(ColumnBatch(n, cols, tuple(kinds), self.dict if self.str_keys else None,
+                                   np.full(n, end - 1, dtype=np.int64), self._subtasks(keys), False))
+        return out
+
+    def process(self, items):
+        if self.fallback is not None:
+            return self.fallback.process(expand_columns(items))
+        out = []
+        for i, it in enumerate(items):
+            if isinstance(it, WM):
+                out.extend(self._flush())
+                if self.fallback is not None:
+                    # the flush switched to the host operator: it takes the rest of the pass
+                    return out + self.fallback.process(expand_columns(items[i:]))
+                self.wm = it.ts
+                if self.op is not None:
+                    out.extend(self._emit(self.op.advance_watermark(it.ts)))
+                out.append(it)
+            else:
+                self.pending.append(it)
+        out.extend(self._flush())
+        return out
+
+    def on_processing_time(self, now):
+        if self.fallback is not None:
+            return self.fallback.on_processing_time(now)
+        return self._flush()
+
+    def finish(self):
+        if self.fallback is not None:
+            return self.fallback.finish()
+        return self._flush()
+
+    def take_side(self, tag_id):
+        if self.fallback is not None:
+            return self.fallback.take_side(tag_id)
+        return super().take_side(tag_id)
+
+    def snapshot(self) -> dict:
+        """Both arenas' rows (KeyedJoinWindowOperator.snapshot_state), the key dictionary and both
+        sides' value kinds; or the exact host operator's state after a fallback."""
+        if self.pending:
+            raise RuntimeError("snapshot between micro-batches only (records pending)")
+        if self.fallback is not None:
+            return {"fallback": self.fallback.snapshot()}
+        snap = {"wm": self.wm, "late": self._late, "str_keys": self.str_keys,
+                "strings": list(self.dict.strings()), "is_float": list(self.is_float)}
+        if self.op is not None:
+            es = self.op.snapshot_state()
+            snap["engine"] = {"columns": es.columns, "meta": es.meta}
+        return snap
+
+    def restore(self, snap: dict) -> None:
+        if "fallback" in snap:
+            if self.fallback is None:
+                self._to_fallback()
+            self.fallback.restore(snap["fallback"])
+            return
+        self.wm, self._late, self.str_keys = snap["wm"], snap["late"], snap["str_keys"]
+        self.is_float = list(snap["is_float"])
+        for st in snap["strings"]:
+            self.dict.intern(st)
+        eng = snap.get("engine")
+        if eng is not None:
+            self._build()
+            self.op.restore_state(eng["columns"], eng["meta"])
