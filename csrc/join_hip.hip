@@ -15,6 +15,7 @@
 #include <string>
 
 #include "mxs_join.h"
+#include "mxs_blockscan.h"
 
 namespace mxs {
 namespace {
@@ -62,44 +63,6 @@ __global__ __launch_bounds__(256) void join_match_kernel(
 // ---- scan (64-bit, saturating; the tiles + one-workgroup tile scan of lw_scan) ---------------
 constexpr int kScanThreads = 1024;
 constexpr int kScanPer = kJoinScanTile / kScanThreads;  // 4 segments per thread
-
-struct SatAdd {
-  __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const {
-    return join_sat_add(a, b);
-  }
-};
-struct Add32 {
-  __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
-};
-
-// Block-wide exclusive scan of one value per thread (1024 threads) under an associative `op`
-// with identity 0: wave shuffles + wave totals.
-template <class T, class Op>
-__device__ __forceinline__ T block_excl_scan(T v, T* wsum, T* total, Op op) {
-  T incl = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(incl, d);
-    if ((int)(threadIdx.x & 63) >= d) incl = op(y, incl);
-  }
-  T excl = __shfl_up(incl, 1);
-  if ((threadIdx.x & 63) == 0) excl = 0;
-  const int wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 63) wsum[wv] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    T t = 0;
-    for (int i = 0; i < nw; ++i) {
-      const T c = wsum[i];
-      wsum[i] = t;
-      t = op(t, c);
-    }
-    *total = t;
-  }
-  __syncthreads();
-  const T r = op(wsum[wv], excl);
-  __syncthreads();
-  return r;
-}
 
 // Pass 1: per tile, the pair total and the number of matched (non-empty) segments.
 __global__ __launch_bounds__(kScanThreads) void join_tile_sums_kernel(

@@ -1,0 +1,51 @@
+// mxstream — the block-wide exclusive scan and the two scan operators that the pair scans of the
+// window join (csrc/join_hip.hip) and of the interval join (csrc/ijoin_hip.hip) share.
+// Device code only: include from a .hip file after mxs_join.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "mxs_join.h"
+
+namespace mxs {
+
+struct SatAdd {
+  __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const {
+    return join_sat_add(a, b);
+  }
+};
+struct Add32 {
+  __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
+};
+
+// Block-wide exclusive scan of one value per thread (up to 1024 threads) under an associative
+// `op` with identity 0: wave shuffles + wave totals. `wsum` holds one word per wave.
+template <class T, class Op>
+__device__ __forceinline__ T block_excl_scan(T v, T* wsum, T* total, Op op) {
+  T incl = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const T y = __shfl_up(incl, d);
+    if ((int)(threadIdx.x & 63) >= d) incl = op(y, incl);
+  }
+  T excl = __shfl_up(incl, 1);
+  if ((threadIdx.x & 63) == 0) excl = 0;
+  const int wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if ((threadIdx.x & 63) == 63) wsum[wv] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    T t = 0;
+    for (int i = 0; i < nw; ++i) {
+      const T c = wsum[i];
+      wsum[i] = t;
+      t = op(t, c);
+    }
+    *total = t;
+  }
+  __syncthreads();
+  const T r = op(wsum[wv], excl);
+  __syncthreads();
+  return r;
+}
+
+}  // namespace mxs

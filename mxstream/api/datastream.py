@@ -273,6 +273,10 @@ class KeyedStream(DataStream):
         op.t.key_fn_in = self.key_fn  # hash-partitioned edge (multi-rank record exchange)
         return op
 
+    def _one_input_plain(self, name: str, factory):
+        """An operator behind a forward edge (the tag of an interval join: the union is keyed)."""
+        return super()._one_input(name, factory)
+
     # -- rolling aggregations (StreamGroupedReduce: emit per element) --
     def reduce(self, fn) -> SingleOutputStreamOperator:
         key_fn = self.key_fn
@@ -356,6 +360,14 @@ class KeyedStream(DataStream):
             return ws.trigger(W.PurgingTrigger.of(W.CountTrigger.of(size)))
         return ws.evictor(W.CountEvictor.of(size)).trigger(W.CountTrigger.of(slide))
 
+    # -- interval join --
+    def interval_join(self, other: "KeyedStream"):
+        """Interval join (api/joins.py): ``a.interval_join(b).between(lo, hi).process(fn)``."""
+        from .joins import IntervalJoin
+
+        return IntervalJoin(self, other)
+
+    intervalJoin = interval_join
     maxBy = max_by
     minBy = min_by
     timeWindow = time_window

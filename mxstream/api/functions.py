@@ -272,6 +272,39 @@ class KeyedProcessFunction(ProcessFunction):
     pass
 
 
+class ProcessJoinFunction(RichFunction):
+    """process_element(left, right, ctx, out), once per pair of an interval join
+    (``a.interval_join(b).between(lo, hi).process(fn)``)."""
+
+    class Context:
+        def __init__(self, left_ts: int, right_ts: int, side_outputs):
+            self._left, self._right = left_ts, right_ts
+            self._side = side_outputs
+
+        def get_left_timestamp(self) -> int:
+            return self._left
+
+        def get_right_timestamp(self) -> int:
+            return self._right
+
+        def get_timestamp(self) -> int:
+            """The pair's timestamp: the larger of the two elements'."""
+            return max(self._left, self._right)
+
+        def output(self, tag, value):
+            self._side.setdefault(tag.tag_id, []).append(value)
+
+        getLeftTimestamp = get_left_timestamp
+        getRightTimestamp = get_right_timestamp
+        getTimestamp = get_timestamp
+
+    def process_element(self, left, right, ctx, out: Collector):
+        raise NotImplementedError
+
+    def processElement(self, left, right, ctx, out):
+        return self.process_element(left, right, ctx, out)
+
+
 class SinkFunction(Function):
     def invoke(self, value, context=None):
         raise NotImplementedError

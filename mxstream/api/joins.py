@@ -11,6 +11,10 @@ side (runtime/columnar.py TagSideOp), unioned (watermark = the minimum of the tw
 by the side's own selector, windowed by `assigner` and handed to ``WindowedStream.apply`` with a
 co-group function. The window node carries ``meta = {"kind": "join", ...}``; the planner
 (api/planner.py _lower_join) replaces it by the native operator where it can prove the shape.
+
+``a.key_by(ka).interval_join(b.key_by(kb)).between(lo, hi).process(fn)`` (Flink 1.8
+``KeyedStream.intervalJoin``, below) pairs elements of one key whose timestamps satisfy
+``l.ts + lo <= r.ts <= l.ts + hi``, as they arrive and independent of any window.
 """
 from __future__ import annotations
 
@@ -189,3 +193,78 @@ def _join_as_co_group(fn):
                     out.collect(call(l, r))
 
     return join
+
+
+# ---- interval joins (Flink 1.8 KeyedStream.intervalJoin) ---------------------------------------
+
+class IntervalJoin:
+    """``a.interval_join(b)``: waits for ``between``. Both inputs are keyed streams of one
+    environment; the join is defined in event time only."""
+
+    def __init__(self, left, right):
+        from .datastream import KeyedStream
+        from .time import TimeCharacteristic
+
+        if not isinstance(left, KeyedStream) or not isinstance(right, KeyedStream):
+            raise TypeError("interval_join: both inputs must be keyed streams (key_by first)")
+        if left.env is not right.env:
+            raise ValueError("both inputs must belong to one execution environment")
+        if left.env.time_characteristic != TimeCharacteristic.EventTime:
+            raise RuntimeError("Time-bounded stream joins are only supported in event time")
+        self.left, self.right = left, right
+
+    def between(self, lower, upper) -> "IntervalJoined":
+        from .time import to_ms
+
+        return IntervalJoined(self.left, self.right, to_ms(lower), to_ms(upper))
+
+    def process(self, fn):
+        raise ValueError("process() before between(): name the bounds first")
+
+
+class IntervalJoined:
+    """``...between(lo, hi)[.lower_bound_exclusive()][.upper_bound_exclusive()].process(fn)``:
+    `fn` is a ProcessJoinFunction, or a plain ``fn(left, right) -> value`` that collects that
+    value. The plan: tag(0) / tag(1) -> union -> key_by(the side's own selector) -> the interval
+    join operator (runtime/operators.py IntervalJoinOp), whose node carries
+    ``meta = {"kind": "interval_join", ...}`` for the planner (_lower_interval_join)."""
+
+    def __init__(self, left, right, lo: int, hi: int):
+        self.left, self.right = left, right
+        self.lo, self.hi = int(lo), int(hi)
+        self._check()
+
+    def _check(self) -> None:
+        if self.lo > self.hi:
+            raise ValueError("lowerBound <= upperBound must be fulfilled")
+
+    def lower_bound_exclusive(self) -> "IntervalJoined":
+        self.lo += 1
+        self._check()
+        return self
+
+    def upper_bound_exclusive(self) -> "IntervalJoined":
+        self.hi -= 1
+        self._check()
+        return self
+
+    lowerBoundExclusive = lower_bound_exclusive
+    upperBoundExclusive = upper_bound_exclusive
+
+    def process(self, fn):
+        from ..runtime import operators as O
+        from ..runtime.columnar import TagSideOp
+
+        if not isinstance(fn, F.ProcessJoinFunction) and not callable(fn):
+            raise TypeError("process(): a ProcessJoinFunction or fn(left, right) is expected")
+        ka, kb = self.left.key_fn, self.right.key_fn
+        lo, hi = self.lo, self.hi
+        columnar = {"on": False}  # the planner switches the tag operators to column batches
+        tagged = [s._one_input_plain("Join(tag)", lambda i=i: TagSideOp(i, columnar["on"]))
+                  for i, s in enumerate((self.left, self.right))]
+        key_fn = lambda tv: F.call_key(ka if tv[0] == 0 else kb, tv[1])  # noqa: E731
+        keyed = tagged[0].union(tagged[1]).key_by(key_fn)
+        op = keyed._one_input("IntervalJoin", lambda: O.IntervalJoinOp(key_fn, lo, hi, fn))
+        op.t.meta = {"kind": "interval_join", "fn": fn, "lo": lo, "hi": hi,
+                     "key_pos": (self.left.key_pos, self.right.key_pos), "columnar": columnar}
+        return op

@@ -17,7 +17,9 @@ runs:
 A window join (api/joins.py) whose function is a projection -- a tuple of the key and one value
 field of each side -- over tumbling / sliding event-time windows with both keys given as field
 positions is lowered onto NativeJoinOp (``_lower_join``); any other join, and every co-group,
-keeps the host plan (tagged union -> keyed window -> co-group function).
+keeps the host plan (tagged union -> keyed window -> co-group function). An interval join with
+positional keys and such a projection is lowered onto NativeIntervalJoinOp
+(``_lower_interval_join``); any other keeps the tagged union -> keyed IntervalJoinOp.
 
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
 (``_lower_topn``): the keyed operator cuts each firing to its top-N candidates on the device.
@@ -290,6 +292,9 @@ def plan(env, sinks):
             continue
         if meta.get("kind") == "join":
             _lower_join(env, t, meta)
+            continue
+        if meta.get("kind") == "interval_join":
+            _lower_interval_join(env, t, meta)
             continue
         if meta.get("kind") != "window":
             continue
@@ -854,6 +859,71 @@ def _lower_join(env, t, meta) -> None:
         return NativeJoinOp(key_pos=kp, val_pos=(lval, rval), layout=layout,
                             ok_arities=(frozenset(ok[0]), frozenset(ok[1])), assigner=assigner,
                             device=device, fallback_factory=fallback)
+
+    t.factory = factory
+    t.meta = dict(t.meta, native=True)
+    meta["columnar"]["on"] = True  # the tag operators let column batches through as they are
+
+
+class _PoisonedContext:
+    """The `ctx` of a traced ProcessJoinFunction: any use ends the trace."""
+
+    def __getattr__(self, name):
+        raise TypeError("ctx is not available to a traced join function")
+
+
+def _as_join_fn(fn):
+    """`fn` as a ``(left, right) -> value`` callable for trace_join_projection: a plain callable
+    as it is; a ProcessJoinFunction when it collects exactly one value and leaves `ctx` alone."""
+    from . import functions as F
+
+    if not isinstance(fn, F.ProcessJoinFunction):
+        return fn
+
+    def call(left, right):
+        col = F.Collector()
+        fn.process_element(left, right, _PoisonedContext(), col)
+        if len(col.items) != 1:
+            raise TypeError("not exactly one collect")
+        return col.items[0]
+
+    return call
+
+
+def _lower_interval_join(env, t, meta) -> None:
+    """``a.interval_join(b).between(lo, hi).process(fn)`` -> NativeIntervalJoinOp when both keys
+    are field positions, one rank runs the job and `fn` traces to a projection: exactly one
+    collect of a tuple whose fields are bare key references or the one value field of a side.
+    Anything else keeps the host plan: tagged union -> keyed IntervalJoinOp."""
+    from ..runtime.native_ops import NativeIntervalJoinOp
+
+    kp = meta["key_pos"]
+    comm = getattr(env, "_comm", None)
+    world = comm.world if comm is not None else getattr(env, "world", 1)
+    if kp[0] is None or kp[1] is None or world > 1:
+        return
+    call = _as_join_fn(meta["fn"])
+    shape, ok = None, (set(), set())
+    for side in (0, 1):
+        for ar in range(2, 9):
+            tr = trace_join_projection(call, kp, ar if side == 0 else 8, 8 if side == 0 else ar)
+            if tr is None:
+                continue
+            if shape is None:
+                shape = tr
+            if tr == shape:
+                ok[side].add(ar)
+    if shape is None or not ok[0] or not ok[1]:
+        return
+    layout, lval, rval = shape
+    fallback = t.factory
+    device = env.config.device
+    lo, hi = meta["lo"], meta["hi"]
+
+    def factory():
+        return NativeIntervalJoinOp(key_pos=kp, val_pos=(lval, rval), layout=layout,
+                                    ok_arities=(frozenset(ok[0]), frozenset(ok[1])), lo=lo, hi=hi,
+                                    device=device, fallback_factory=fallback)
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)

@@ -898,6 +898,79 @@ def config13(steps: int, warmup: int, batch: int | None = None, keys: int = 100_
     return res
 
 
+def config14(steps: int, warmup: int, batch: int | None = None, keys: int = 100_000,
+             lo: int = -500, hi: int = 500, zipf: float = 0.0, device: str = "cuda") -> dict:
+    """Keyed interval join at scale: two device-generated streams (two stream ids of gen_events)
+    of `batch` events per side and 1 s step feed KeyedIntervalJoinOperator directly; every batch
+    is sorted, probes the other side's buffer, scans the range lengths, expands every pair into
+    four int64 columns on the device (32 B per pair, nothing copied to the host) and is merged
+    into its own side's buffer; the watermark follows the steps and cleans the buffers.
+
+    Defaults: 100,000 keys, 2**21 events per side and step -- about 21 events per key, side and
+    second -- and bounds (-500, 500) ms: an element meets the other side's elements of one
+    second, so a step yields about 2**21 x 21 = 4.4e7 pairs, config 13's firing. With `zipf` > 0
+    the default batch is 2**15 per side and step, as in config 13.
+    Also timed in the same call: a device fill of one step's output bytes."""
+    from ..runtime.interval_join_operator import KeyedIntervalJoinOperator
+
+    dev = torch.device(device)
+    if batch is None:
+        batch = (1 << 15) if zipf > 0 else (1 << 21)
+    step_ms, disorder = 1_000, 200
+    op = KeyedIntervalJoinOperator(lo=lo, hi=hi, device=dev)
+    cols = [[torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3)] for _ in (0, 1)]
+    t0_event = 1_566_957_600_000
+    state = {"i": 0}
+    lat: list[float] = []
+
+    def step():
+        i = state["i"]
+        t_in = time.perf_counter()
+        n = 0
+        for sd, (kt, tt, vt) in enumerate(cols):
+            K.gen_events(kt, tt, vt, seed=14, stream_id=sd, idx0=i * batch, nkeys=keys,
+                         ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=disorder,
+                         val_lo=0, val_span=10_000, val_f64=True, zipf=zipf)
+            n += sum(int(ch[0].numel()) for ch in op.process(sd, kt, tt, vt))
+        op.advance_watermark(t0_event + (i + 1) * step_ms - disorder - 1)
+        _sync(dev)
+        lat.append((time.perf_counter() - t_in) * 1e3)
+        state["i"] = i + 1
+        return n
+
+    for _ in range(warmup):
+        step()
+    _sync(dev)
+    lat.clear()
+    t0 = time.perf_counter()
+    pairs = 0
+    for _ in range(steps):
+        pairs += step()
+    _sync(dev)
+    dt = time.perf_counter() - t0
+    per_step = pairs // max(1, steps)
+    res = {"config": 14, "metric": "events/sec (keyed interval join, both sides)",
+           "value": 2 * batch * steps / dt, "unit": "events/s", "pairs_per_s": pairs / dt,
+           "ms_per_step": dt / steps * 1e3, "p50_step_ms": statistics.median(lat) if lat else None,
+           "pairs": pairs, "pairs_per_step": per_step, "expand_bytes": 32 * pairs,
+           "buffered_rows": list(op.n), "late_dropped": op.metrics.num_late_records_dropped,
+           "keys": keys, "events_per_side_and_step": batch, "lo_ms": lo, "hi_ms": hi,
+           "zipf": zipf, "device": str(dev)}
+    if per_step:
+        # The same number of bytes written by a plain device fill (the streaming-store yardstick).
+        buf = torch.empty(4 * per_step, dtype=torch.int64, device=dev)
+        buf.fill_(1)
+        _sync(dev)
+        t1 = time.perf_counter()
+        for _ in range(5):
+            buf.fill_(2)
+        _sync(dev)
+        fill_ms = (time.perf_counter() - t1) / 5 * 1e3
+        res["fill_ms_per_step_bytes"] = fill_ms
+        res["fill_GBps"] = 32 * per_step / fill_ms / 1e6
+    return res
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1180,7 +1253,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1198,6 +1271,8 @@ def main(argv=None) -> int:
                     help="config 5: the unpipelined session step")
     ap.add_argument("--revisit", type=float, default=0.0,
                     help="config 5: fraction of events for spilled (long idle) keys")
+    ap.add_argument("--lo", type=int, default=-500, help="config 14: lower bound in ms")
+    ap.add_argument("--hi", type=int, default=500, help="config 14: upper bound in ms")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None,
@@ -1271,6 +1346,9 @@ def main(argv=None) -> int:
     elif a.config == 13:
         r = config13(a.steps, a.warmup, a.batch, keys=a.keys or 100_000, size=a.size or 1_000,
                      slide=a.slide, zipf=a.zipf, device=a.device)
+    elif a.config == 14:
+        r = config14(a.steps, a.warmup, a.batch, keys=a.keys or 100_000, lo=a.lo, hi=a.hi,
+                     zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

@@ -778,3 +778,164 @@ def join_expand(jp: JoinPlan, lord: torch.Tensor, rord: torch.Tensor, p0: int, p
                           jp.match.data_ptr(), jp.pair_off.data_ptr(), lord.data_ptr(),
                           rord.data_ptr(), p0, p1, ok.data_ptr(), ol.data_ptr(), orr.data_ptr())
     return ok, ol, orr
+
+
+# ---- keyed interval joins (csrc/mxs_ijoin.h) ---------------------------------------------------
+
+def sat_add_i64(a: int, b: int) -> int:
+    """a + b saturated at the int64 limits (the interval join's timestamp arithmetic)."""
+    return max(I64_MIN, min(I64_MAX, int(a) + int(b)))
+
+
+def _ijoin_cols(cols, name: str, dev):
+    """(key, ts, val) int64 columns of one length."""
+    k, t, v = cols
+    n = k.numel()
+    for c, nm in ((k, "key"), (t, "ts"), (v, "val")):
+        _check(c, torch.int64, n, f"{name}.{nm}", dev)
+        if c.dim() != 1 or c.numel() != n:
+            raise ValueError(f"{name}.{nm}: one word per row expected")
+    return n
+
+
+@dataclass
+class IJoinPlan:
+    """A probed and scanned batch (``ijoin_plan``): what ``ijoin_expand`` needs to write any range
+    of the batch's P pairs."""
+    side: int               # the batch's side: 0 = left, 1 = right
+    batch: tuple            # (key, ts, val), sorted by (key, ts)
+    other: tuple            # the other side's buffer (key, ts, val)
+    lb: torch.Tensor        # int64 [n]: the first row of each element's range in `other`
+    cnt: torch.Tensor       # int64 [n]: the length of the range
+    plan: torch.Tensor      # int64 [IJOIN_PLAN_COLS * (n + 1)]: the non-empty elements, compacted
+    pairs: int              # P
+    rows: int               # m
+
+
+def ijoin_probe(bkey: torch.Tensor, bts: torch.Tensor, okey: torch.Tensor, ots: torch.Tensor,
+                rlo: int, rhi: int, cutoff: int = I64_MIN):
+    """Every batch element's range in the other side's buffer: ``lb`` = the first row >=
+    (k, max(t + rlo, cutoff + 1)), ``cnt`` = the rows from there up to (k, t + rhi). Sums
+    saturate; rows with ts <= cutoff are expired and never counted."""
+    dev = bkey.device
+    nb, no = bkey.numel(), okey.numel()
+    _check(bkey, torch.int64, nb, "bkey", dev)
+    _check(bts, torch.int64, nb, "bts", dev)
+    _check(okey, torch.int64, no, "okey", dev)
+    _check(ots, torch.int64, no, "ots", dev)
+    if bts.numel() != nb or ots.numel() != no:
+        raise ValueError("ijoin_probe: one timestamp per key expected")
+    for b in (rlo, rhi, cutoff):
+        if not I64_MIN <= int(b) <= I64_MAX:
+            raise ValueError("ijoin_probe: bounds must be int64")
+    lb = torch.empty(nb, dtype=torch.int64, device=dev)
+    cnt = torch.empty(nb, dtype=torch.int64, device=dev)
+    cuda = _is_gpu(bkey)
+    load().ijoin_probe(cuda, _p(bkey), _p(bts), nb, _p(okey), _p(ots), no, int(rlo), int(rhi),
+                       int(cutoff), _p(lb), _p(cnt), _stream(bkey) if cuda else 0)
+    return lb, cnt
+
+
+def ijoin_scan(cnt: torch.Tensor, lb: torch.Tensor):
+    """Exclusive 64-bit saturating scan of the counts and the non-empty elements compacted:
+    (plan, P, m, error word). One readback."""
+    dev = cnt.device
+    n = cnt.numel()
+    _check(cnt, torch.int64, n, "cnt", dev)
+    _check(lb, torch.int64, n, "lb", dev)
+    m = load()
+    plan = torch.empty(m.IJOIN_PLAN_COLS * (n + 1), dtype=torch.int64, device=dev)
+    meta = torch.zeros(m.IJOIN_META, dtype=torch.int64, device=dev)
+    scratch = torch.empty(max(16, m.ijoin_scan_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    cuda = _is_gpu(cnt)
+    m.ijoin_scan(cuda, _p(cnt), _p(lb), n, _p(scratch), _p(plan), _p(meta),
+                 _stream(cnt) if cuda else 0)
+    pairs, rows, err, _ = meta.tolist()
+    return plan, pairs, rows, err
+
+
+def ijoin_plan(side: int, batch, other, lo: int, hi: int, cutoff: int = I64_MIN) -> IJoinPlan:
+    """Probe `other` (the other side's buffer) with the sorted `batch` of `side` under the
+    bounds l.ts + lo <= r.ts <= l.ts + hi and scan the counts. 2**62 pairs or more raise
+    OverflowError before anything is expanded."""
+    if side not in (0, 1):
+        raise ValueError("side must be 0 (left) or 1 (right)")
+    dev = batch[0].device
+    _ijoin_cols(batch, "batch", dev)
+    _ijoin_cols(other, "other", dev)
+    rlo, rhi = (lo, hi) if side == 0 else (sat_add_i64(0, -int(hi)), sat_add_i64(0, -int(lo)))
+    lb, cnt = ijoin_probe(batch[0], batch[1], other[0], other[1], rlo, rhi, cutoff)
+    plan, pairs, rows, err = ijoin_scan(cnt, lb)
+    if err or pairs >= load().JOIN_MAX_PAIRS:
+        raise OverflowError("interval join: a batch of 2**62 pairs or more")
+    return IJoinPlan(side, tuple(batch), tuple(other), lb, cnt, plan, pairs, rows)
+
+
+def ijoin_expand(jp: IJoinPlan, p0: int, p1: int):
+    """Pairs [p0, p1) of the planned batch as four int64 columns of p1 - p0 rows: the key id, the
+    left and the right value bits and max(l.ts, r.ts). Batch elements in order, each with its
+    partners in the other buffer's order."""
+    dev = jp.lb.device
+    p0, p1 = int(p0), int(p1)
+    if not 0 <= p0 <= p1 <= jp.pairs:
+        raise ValueError(f"pair range [{p0}, {p1}) outside [0, {jp.pairs})")
+    n = p1 - p0
+    out = torch.empty((4, n + (n & 1)), dtype=torch.int64, device=dev)[:, :n]  # 16-byte columns
+    ok, ol, orr, ot = out[0], out[1], out[2], out[3]
+    if n == 0:
+        return ok, ol, orr, ot
+    bk, bt, bv = jp.batch
+    _, ots, ov = jp.other
+    m = load()
+    if _is_gpu(jp.lb):
+        m.gpu_ijoin_expand(_p(jp.plan), bk.numel(), jp.rows, jp.pairs, _p(bk), _p(bt), _p(bv),
+                           _p(ots), _p(ov), ots.numel(), jp.side, p0, p1, _p(ok), _p(ol), _p(orr),
+                           _p(ot), _stream(jp.lb))
+    else:
+        m.cpu_ijoin_expand(_p(jp.cnt), _p(jp.lb), _p(bk), _p(bt), _p(bv), bk.numel(), _p(ots),
+                           _p(ov), ots.numel(), jp.side, p0, p1, _p(ok), _p(ol), _p(orr), _p(ot))
+    return ok, ol, orr, ot
+
+
+def ijoin_merge(old, batch, out: torch.Tensor) -> int:
+    """Merge the sorted `batch` into the sorted buffer `old` (both (key, ts, val)) into the rows
+    of `out` (int64 [3, cap]); on equal (key, ts) the old rows stay first. Returns the row count."""
+    dev = out.device
+    no = _ijoin_cols(old, "old", dev)
+    nb = _ijoin_cols(batch, "batch", dev)
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != 3 \
+            or out.shape[1] < no + nb or not out.is_contiguous():
+        raise ValueError("ijoin_merge: out must be a contiguous int64 [3, >= rows] tensor")
+    for c in (*old, *batch):
+        if c.numel() and c.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+            raise ValueError("ijoin_merge: out must not alias an input")
+    cuda = _is_gpu(out)
+    load().ijoin_merge(cuda, *(_p(c) for c in old), no, *(_p(c) for c in batch), nb,
+                       _p(out[0]), _p(out[1]), _p(out[2]), _stream(out) if cuda else 0)
+    return no + nb
+
+
+def ijoin_purge(src, cutoff: int, out: torch.Tensor) -> int:
+    """Order-preserving compaction of the rows of `src` (key, ts, val) with ts > cutoff into the
+    rows of `out` (int64 [3, cap >= rows]). Returns the number of survivors (one readback)."""
+    dev = out.device
+    n = _ijoin_cols(src, "src", dev)
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != 3 or out.shape[1] < n \
+            or not out.is_contiguous():
+        raise ValueError("ijoin_purge: out must be a contiguous int64 [3, >= rows] tensor")
+    for c in src:
+        if c.numel() and c.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+            raise ValueError("ijoin_purge: out must not alias an input")
+    m = load()
+    if not _is_gpu(out):
+        return m.cpu_ijoin_purge(*(_p(c) for c in src), n, int(cutoff), _p(out[0]), _p(out[1]),
+                                 _p(out[2]))
+    if n == 0:
+        return 0
+    st = _stream(out)
+    keep = torch.empty(n, dtype=torch.int64, device=dev)
+    m.gpu_ijoin_keep(_p(src[1]), n, int(cutoff), _p(keep), st)
+    plan, _, rows, _ = ijoin_scan(keep, keep)
+    m.gpu_ijoin_gather(_p(plan), n, rows, *(_p(c) for c in src), _p(out[0]), _p(out[1]),
+                       _p(out[2]), st)
+    return rows

@@ -2012,33 +2012,24 @@ class NativeVectorWindowOp(NativeWindowOp):
         self.op.restore_state(eng["columns"], eng["meta"])
 
 
-class NativeJoinOp(Operator):
-    """``a.join(b).where(p).equal_to(q).window(tumbling | sliding event time).apply(fn)`` on the
-    device join operator (runtime/join_window_operator.py) when `fn` is a projection: a tuple of
-    the key and one value field of each side (planner._lower_join). Input is the tagged union of
-    the host plan (records ``(side, value)``, or column batches that carry their side); each
-    side keeps its (key id, timestamp, value bits) rows in a pane arena of its own, and a firing
-    matches the key segments and expands every matched key's pairs on the device.
+class _NativeTwoSidedOp(Operator):
+    """What the native join operators share (NativeJoinOp, NativeIntervalJoinOp). Input is the
+    tagged union of the host plan (records ``(side, value)``, or column batches that carry their
+    side). One dictionary, owned by the operator, holds both sides' string keys, with tables that
+    translate every upstream dictionary's ids; each side has a value kind of its own (doubles, or
+    integers as the bit pattern of ``float(x)``, exact for |x| <= 2**53, that come back as
+    longs). Unsupported data switches to the host operator before native state exists and raises
+    afterwards. A subclass builds the engine operator (``_build``), feeds it the pending items'
+    columns (``_feed``) and says what a watermark emits (``_on_watermark``)."""
 
-    One dictionary, owned by the operator, holds both sides' string keys: the ids of every
-    upstream dictionary are translated through a table that grows with that dictionary (a name is
-    interned once, a device batch is translated on the device), so nothing is ever interned into
-    a parser's dictionary. Each side has a value kind of
-    its own: doubles, or integers carried as the bit pattern of ``float(x)`` (exact for
-    |x| <= 2**53) that come back as longs. Mixed key types, a non-numeric value, an integer
-    beyond 2**53 or a wrong arity switch to the host operator before native state exists and
-    raise afterwards. Output: one host ColumnBatch per fired chunk in `fn`'s layout."""
-
-    name = "Window(native join)"
     accepts_columns = True
     _INT_EXACT = 1 << 53
 
-    def __init__(self, *, key_pos, val_pos, layout, ok_arities, assigner, device: str,
-                 fallback_factory, pair_chunk: int = 1 << 24):
+    def __init__(self, *, key_pos, val_pos, layout, ok_arities, device: str, fallback_factory,
+                 pair_chunk: int = 1 << 24):
         self.key_positions, self.val_positions = tuple(key_pos), tuple(val_pos)
         self.layout = tuple(layout)            # "k" | "l" | "r" per output field
         self.ok_arities = tuple(ok_arities)    # per side
-        self.assigner = assigner
         self.device = device
         self.fallback_factory = fallback_factory
         self.pair_chunk = pair_chunk
@@ -2112,14 +2103,6 @@ class NativeJoinOp(Operator):
         if device:
             return torch.from_numpy(tab).to(col.device)[col.to(torch.int64)]
         return tab[col]
-
-    def _build(self) -> None:
-        from .join_window_operator import KeyedJoinWindowOperator
-
-        a = self.assigner
-        self.op = KeyedJoinWindowOperator(size=a.size, slide=a.slide, offset=a.offset,
-                                          device=torch.device(self.device),
-                                          pair_chunk=self.pair_chunk)
 
     # -- input: one side's pending items as (key ids, timestamps, value bits) -------------------
     def _kind(self, side: int, is_float: bool, kinds: list) -> None:
@@ -2232,37 +2215,31 @@ class NativeJoinOp(Operator):
         self.is_float = kinds
         if self.op is None:
             self._build()
-        dev = self.op.device
-        to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray)  # noqa: E731
-                            else x).to(dev)
-        for side in (0, 1):
-            mine = [p for p in parts if p[0] == side]
-            if not mine:
-                continue
-            cols = [torch.cat([to_dev(p[j]) for p in mine]) for j in (1, 2, 3)]
-            self.op.process(side, *cols)
+        out = self._feed(parts)
         self._late = self.op.metrics.num_late_records_dropped
-        return []
+        return out
+
+    def _to_dev(self, x):
+        return (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray)
+                else x).to(self.op.device)
 
     # -- output ---------------------------------------------------------------------------------
-    def _emit(self, fired) -> list:
-        out = []
-        for _s, end, keys, lv, rv in fired:
-            keys, lv, rv = (x.cpu().numpy() for x in (keys, lv, rv))
-            cols, kinds = [], []
-            for f in self.layout:
-                if f == "k":
-                    cols.append(keys)
-                    kinds.append(FK_STR if self.str_keys else FK_LONG)
-                else:
-                    bits, is_float = (lv, self.is_float[0]) if f == "l" else (rv, self.is_float[1])
-                    vals = np.ascontiguousarray(bits).view(np.float64)
-                    cols.append(vals if is_float else vals.astype(np.int64))
-                    kinds.append(FK_DOUBLE if is_float else FK_LONG)
-            n = int(keys.size)
-            out.append(ColumnBatch(n, cols, tuple(kinds), self.dict if self.str_keys else None,
-                                   np.full(n, end - 1, dtype=np.int64), self._subtasks(keys), False))
-        return out
+    def _columns(self, keys, lv, rv, ts) -> ColumnBatch:
+        """One host ColumnBatch in `fn`'s layout from device columns (key ids, left and right
+        value bits) and the rows' timestamps (a numpy array)."""
+        keys, lv, rv = (x.cpu().numpy() for x in (keys, lv, rv))
+        cols, kinds = [], []
+        for f in self.layout:
+            if f == "k":
+                cols.append(keys)
+                kinds.append(FK_STR if self.str_keys else FK_LONG)
+            else:
+                bits, is_float = (lv, self.is_float[0]) if f == "l" else (rv, self.is_float[1])
+                vals = np.ascontiguousarray(bits).view(np.float64)
+                cols.append(vals if is_float else vals.astype(np.int64))
+                kinds.append(FK_DOUBLE if is_float else FK_LONG)
+        return ColumnBatch(int(keys.size), cols, tuple(kinds),
+                           self.dict if self.str_keys else None, ts, self._subtasks(keys), False)
 
     def process(self, items):
         if self.fallback is not None:
@@ -2276,7 +2253,7 @@ class NativeJoinOp(Operator):
                     return out + self.fallback.process(expand_columns(items[i:]))
                 self.wm = it.ts
                 if self.op is not None:
-                    out.extend(self._emit(self.op.advance_watermark(it.ts)))
+                    out.extend(self._on_watermark(it.ts))
                 out.append(it)
             else:
                 self.pending.append(it)
@@ -2299,8 +2276,8 @@ class NativeJoinOp(Operator):
         return super().take_side(tag_id)
 
     def snapshot(self) -> dict:
-        """Both arenas' rows (KeyedJoinWindowOperator.snapshot_state), the key dictionary and both
-        sides' value kinds; or the exact host operator's state after a fallback."""
+        """The engine operator's rows (its snapshot_state), the key dictionary and both sides'
+        value kinds; or the exact host operator's state after a fallback."""
         if self.pending:
             raise RuntimeError("snapshot between micro-batches only (records pending)")
         if self.fallback is not None:
@@ -2326,3 +2303,87 @@ class NativeJoinOp(Operator):
         if eng is not None:
             self._build()
             self.op.restore_state(eng["columns"], eng["meta"])
+
+
+class NativeJoinOp(_NativeTwoSidedOp):
+    """``a.join(b).where(p).equal_to(q).window(tumbling | sliding event time).apply(fn)`` on the
+    device join operator (runtime/join_window_operator.py) when `fn` is a projection: a tuple of
+    the key and one value field of each side (planner._lower_join). Input is the tagged union of
+    the host plan (records ``(side, value)``, or column batches that carry their side); each
+    side keeps its (key id, timestamp, value bits) rows in a pane arena of its own, and a firing
+    matches the key segments and expands every matched key's pairs on the device.
+
+    One dictionary, owned by the operator, holds both sides' string keys: the ids of every
+    upstream dictionary are translated through a table that grows with that dictionary (a name is
+    interned once, a device batch is translated on the device), so nothing is ever interned into
+    a parser's dictionary. Each side has a value kind of
+    its own: doubles, or integers carried as the bit pattern of ``float(x)`` (exact for
+    |x| <= 2**53) that come back as longs. Mixed key types, a non-numeric value, an integer
+    beyond 2**53 or a wrong arity switch to the host operator before native state exists and
+    raise afterwards. Output: one host ColumnBatch per fired chunk in `fn`'s layout."""
+
+    name = "Window(native join)"
+
+    def __init__(self, *, assigner, **kw):
+        super().__init__(**kw)
+        self.assigner = assigner
+
+    def _build(self) -> None:
+        from .join_window_operator import KeyedJoinWindowOperator
+
+        a = self.assigner
+        self.op = KeyedJoinWindowOperator(size=a.size, slide=a.slide, offset=a.offset,
+                                          device=torch.device(self.device),
+                                          pair_chunk=self.pair_chunk)
+
+    def _feed(self, parts) -> list:
+        for side in (0, 1):
+            mine = [p for p in parts if p[0] == side]
+            if not mine:
+                continue
+            cols = [torch.cat([self._to_dev(p[j]) for p in mine]) for j in (1, 2, 3)]
+            self.op.process(side, *cols)
+        return []
+
+    def _on_watermark(self, wm: int) -> list:
+        return [self._columns(keys, lv, rv, np.full(int(keys.numel()), end - 1, dtype=np.int64))
+                for _s, end, keys, lv, rv in self.op.advance_watermark(wm)]
+
+
+class NativeIntervalJoinOp(_NativeTwoSidedOp):
+    """``a.interval_join(b).between(lo, hi).process(fn)`` on the device operator
+    (runtime/interval_join_operator.py) when `fn` is a projection: a tuple of the key and one
+    value field of each side (planner._lower_interval_join). The pending items are fed as
+    maximal runs of one side in arrival order, so a run sees exactly the other side's elements
+    of earlier runs; every chunk of pairs comes out as one host ColumnBatch in `fn`'s layout,
+    timestamped max(l.ts, r.ts). A watermark only moves the clean-up cut-offs."""
+
+    name = "IntervalJoin(native)"
+
+    def __init__(self, *, lo: int, hi: int, **kw):
+        super().__init__(**kw)
+        self.lo, self.hi = int(lo), int(hi)
+
+    def _build(self) -> None:
+        from .interval_join_operator import KeyedIntervalJoinOperator
+
+        self.op = KeyedIntervalJoinOperator(lo=self.lo, hi=self.hi,
+                                            device=torch.device(self.device),
+                                            pair_chunk=self.pair_chunk)
+        if self.wm > LONG_MIN:
+            self.op.advance_watermark(self.wm)  # records are late against it from the start
+
+    def _feed(self, parts) -> list:
+        out, i = [], 0
+        while i < len(parts):
+            j = i
+            while j < len(parts) and parts[j][0] == parts[i][0]:
+                j += 1
+            cols = [torch.cat([self._to_dev(p[c]) for p in parts[i:j]]) for c in (1, 2, 3)]
+            for keys, lv, rv, ts in self.op.process(parts[i][0], *cols):
+                out.append(self._columns(keys, lv, rv, ts.cpu().numpy()))
+            i = j
+        return out
+
+    def _on_watermark(self, wm: int) -> list:
+        return self.op.advance_watermark(wm)

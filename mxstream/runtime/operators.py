@@ -460,6 +460,101 @@ class KeyedProcessOp(KeyedOperator):
         self.wm = snap.get("wm", LONG_MIN)
 
 
+def _sat_add(a: int, b: int) -> int:
+    return max(LONG_MIN, min(LONG_MAX, a + b))
+
+
+class IntervalJoinOp(KeyedOperator):
+    """IntervalJoinOperator (Flink 1.8): the input is the tagged union ``(side, value)`` of both
+    streams, keyed by each side's own selector. Per key and side a buffer ``ts -> [values]``; an
+    element is joined at once with the other side's buffered elements whose timestamps lie in
+    its range (a pair matches iff ``l.ts + lo <= r.ts <= l.ts + hi``), then buffered with a
+    clean-up timer at ``ts + max(hi, 0)`` (left) or ``ts + max(-lo, 0)`` (right), one timer
+    namespace per side. Sums saturate at the long limits. An element behind the watermark is
+    dropped and counted. `fn` is a ProcessJoinFunction or a plain ``fn(left, right) -> value``."""
+
+    name = "IntervalJoin"
+    _TABLES = ("_ij_left", "_ij_right")
+    _NS = ("CLEANUP_LEFT", "CLEANUP_RIGHT")
+
+    def __init__(self, key_fn, lo: int, hi: int, fn):
+        super().__init__(key_fn)
+        self.lo, self.hi = int(lo), int(hi)
+        if self.lo > self.hi:
+            raise ValueError("lowerBound <= upperBound must be fulfilled")
+        self.fn = fn
+        self.wm = LONG_MIN
+        self.num_late_records_dropped = 0
+
+    def open(self, ctx):
+        super().open(ctx)
+        self.timers = _Timers()
+        _open_fn(self.fn, ctx, state_backend=self.backend)
+
+    def on_record(self, r):
+        side, value = r.value
+        ts = r.ts
+        if ts == LONG_MIN:
+            raise RuntimeError("Long.MIN_VALUE timestamp: Elements used in interval stream joins "
+                               "need to have timestamps meaningful timestamps.")
+        if self.wm != LONG_MIN and ts < self.wm:
+            self.num_late_records_dropped += 1
+            return []
+        key = F.call_key(self.key_fn, r.value)
+        self.backend.set_current_key(key)
+        self.backend.set_current_namespace(None)
+        rlo, rhi = (self.lo, self.hi) if side == 0 else (-self.hi, -self.lo)
+        first, last = _sat_add(ts, rlo), _sat_add(ts, rhi)
+        col = F.Collector()
+        out, sub = [], self.subtask_of(key)
+        process = isinstance(self.fn, F.ProcessJoinFunction)
+        for ots, values in self.backend._table(self._TABLES[1 - side]).get((key, None), {}).items():
+            if ots < first or ots > last:
+                continue
+            for other in values:
+                left, right = (value, other) if side == 0 else (other, value)
+                lts, rts = (ts, ots) if side == 0 else (ots, ts)
+                if process:
+                    tagged: dict = {}
+                    self.fn.process_element(
+                        left, right, F.ProcessJoinFunction.Context(lts, rts, tagged), col)
+                    for tag_id, vals in tagged.items():  # side outputs carry the pair's timestamp
+                        self.side.setdefault(tag_id, []).extend(
+                            Rec(v, max(lts, rts), sub) for v in vals)
+                else:
+                    col.collect(self.fn(left, right))
+                out.extend(Rec(v, max(lts, rts), sub) for v in col.items)
+                col.items.clear()
+        self.backend._table(self._TABLES[side]).setdefault((key, None), {}) \
+            .setdefault(ts, []).append(value)
+        keep = max(self.hi, 0) if side == 0 else max(-self.lo, 0)
+        self.timers.reg("event", _sat_add(ts, keep), key, (self._NS[side], ts))
+        return out
+
+    def on_watermark(self, wm):
+        self.wm = wm
+        for _t, key, (ns, ts) in self.timers.pop_due("event", wm):
+            table = self.backend._table(self._TABLES[self._NS.index(ns)])
+            buf = table.get((key, None))
+            if buf is not None:
+                buf.pop(ts, None)
+                if not buf:
+                    del table[(key, None)]
+        return []
+
+    def snapshot(self):
+        return {"keyed": self.backend.snapshot(), "timers": self.timers.snapshot(), "wm": self.wm,
+                "late": self.num_late_records_dropped, "bounds": (self.lo, self.hi)}
+
+    def restore(self, snap):
+        if tuple(snap.get("bounds", (self.lo, self.hi))) != (self.lo, self.hi):
+            raise ValueError("checkpoint of a different interval join")
+        super().restore(snap)
+        self.timers.restore(snap.get("timers", {}))
+        self.wm = snap.get("wm", LONG_MIN)
+        self.num_late_records_dropped = snap.get("late", 0)
+
+
 # ---- windows ------------------------------------------------------------------------------
 
 @dataclass
