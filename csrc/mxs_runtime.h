@@ -13,5 +13,6 @@ void bind_format(pybind11::module_& m);
 void bind_listwin(pybind11::module_& m);
 void bind_join(pybind11::module_& m);
 void bind_ijoin(pybind11::module_& m);
+void bind_lookup(pybind11::module_& m);
 void bind_window_tier(pybind11::module_& m);
 void bind_window_control(pybind11::module_& m);

@@ -106,6 +106,13 @@ class DataStream:
 
     coGroup = co_group
 
+    def connect(self, other: "DataStream"):
+        """Connected streams (api/connect.py): ``a.connect(b)[.key_by(k1, k2)].process(fn)``;
+        keyed at once when both inputs are keyed streams."""
+        from .connect import ConnectedStreams
+
+        return ConnectedStreams(self, other)
+
     def rebalance(self) -> "DataStream":
         return self._one_input("Rebalance", lambda: O.RebalanceOp(self.env.config.rebalance_start))
 

@@ -305,6 +305,150 @@ class ProcessJoinFunction(RichFunction):
         return self.process_element(left, right, ctx, out)
 
 
+class CoMapFunction(Function):
+    """map1(value) / map2(value): one result per element of the first / second connected stream
+    (``a.connect(b).map(fn)``)."""
+
+    def map1(self, value):
+        raise NotImplementedError
+
+    def map2(self, value):
+        raise NotImplementedError
+
+
+class CoFlatMapFunction(Function):
+    """flat_map1(value, out) / flat_map2(value, out): any number of results per element."""
+
+    def flat_map1(self, value, out: "Collector"):
+        raise NotImplementedError
+
+    def flat_map2(self, value, out: "Collector"):
+        raise NotImplementedError
+
+    def flatMap1(self, value, out):
+        return self.flat_map1(value, out)
+
+    def flatMap2(self, value, out):
+        return self.flat_map2(value, out)
+
+
+class CoProcessFunction(RichFunction):
+    """process_element1 / process_element2 (value, ctx, out) for the two connected streams and
+    on_timer(timestamp, ctx, out); on keyed connected streams both inputs share one keyed state
+    and one timer service (``a.connect(b).key_by(k1, k2).process(fn)``)."""
+
+    class Context:
+        def __init__(self, ts, timer_service, side_outputs, key=None):
+            self._ts = ts
+            self._timers = timer_service
+            self._side = side_outputs
+            self._key = key
+
+        def timestamp(self):
+            return self._ts
+
+        def timer_service(self):
+            return self._timers
+
+        def output(self, tag, value):
+            self._side.setdefault(tag.tag_id, []).append(value)
+
+        def get_current_key(self):
+            """The key of keyed connected streams (None otherwise)."""
+            return self._key
+
+        timerService = timer_service
+        getCurrentKey = get_current_key
+
+    class OnTimerContext(Context):
+        def __init__(self, ts, timer_service, side_outputs, time_domain, key=None):
+            super().__init__(ts, timer_service, side_outputs, key)
+            self.time_domain = time_domain
+
+        timeDomain = property(lambda self: self.time_domain)
+
+    def process_element1(self, value, ctx, out: Collector):
+        raise NotImplementedError
+
+    def process_element2(self, value, ctx, out: Collector):
+        raise NotImplementedError
+
+    def on_timer(self, timestamp: int, ctx, out: Collector):
+        pass
+
+    def processElement1(self, value, ctx, out):
+        return self.process_element1(value, ctx, out)
+
+    def processElement2(self, value, ctx, out):
+        return self.process_element2(value, ctx, out)
+
+    def onTimer(self, timestamp, ctx, out):
+        return self.on_timer(timestamp, ctx, out)
+
+
+_LOOKUP_WHENS = {
+    ">": lambda a, b: a > b, ">=": lambda a, b: a >= b, "<": lambda a, b: a < b,
+    "<=": lambda a, b: a <= b, "==": lambda a, b: a == b, "!=": lambda a, b: a != b,
+}
+
+
+class LookupLatest(CoProcessFunction):
+    """Keyed latest-value lookup over ``samples.connect(rules).key_by(k1, k2)``: input 2 (the
+    rules) stores ``rule[state_field]`` in one ValueState per key and emits nothing; input 1 (the
+    samples) reads the value ``t`` in force for its key -- the stored one, else `default`, else the
+    sample is dropped -- and collects ``Tuple3(key, sample[value_field], t)`` with the sample's
+    timestamp when `when` is None or ``sample[value_field] <when> t`` holds. `when` is one of
+    ``">", ">=", "<", "<=", "==", "!="``; values are int or float (not bool) and compare as Java
+    compares doubles: a NaN on either side is false for every operator but ``!=``, and
+    ``-0.0 == 0.0``. A per-host alert threshold that changes while the job runs:
+
+        samples.connect(rules).key_by(0, 0).process(LookupLatest(2, 1, when=">"))
+
+    The planner runs exactly this class (not a subclass) with positional keys on the device
+    lookup operator (runtime/lookup_operator.py); these methods are the exact host
+    implementation used otherwise."""
+
+    def __init__(self, value_field: int, state_field: int, when=None, default=None):
+        for name, f in (("value_field", value_field), ("state_field", state_field)):
+            if isinstance(f, bool) or not isinstance(f, int) or f < 0:
+                raise ValueError(f"LookupLatest: {name} is a non-negative int, got {f!r}")
+        if when is not None and (not isinstance(when, str) or when not in _LOOKUP_WHENS):
+            raise ValueError("LookupLatest: when must be one of '>', '>=', '<', '<=', '==', '!=' "
+                             f"or None, got {when!r}")
+        if default is not None:
+            self._number(default, "default")
+        self.value_field, self.state_field = value_field, state_field
+        self.when, self.default = when, default
+        self.native = ("lookup", value_field, state_field, when, default)
+
+    @staticmethod
+    def _number(x, what: str):
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise TypeError(f"LookupLatest: {what} must be an int or a float, got {x!r}")
+        return x
+
+    def open(self, parameters=None):
+        from .state import ValueStateDescriptor
+
+        self._state = self.get_runtime_context().get_state(ValueStateDescriptor("lookup-latest"))
+
+    def process_element2(self, rule, ctx, out):
+        self._state.update(self._number(rule[self.state_field], "the rule's value"))
+
+    def process_element1(self, sample, ctx, out):
+        from .tuples import Tuple3
+
+        t = self._state.value()
+        if t is None:
+            t = self.default
+        if t is None:
+            return
+        v = self._number(sample[self.value_field], "the sample's value")
+        # Python compares an int with a float exactly; Java compares the two doubles
+        if self.when is None or _LOOKUP_WHENS[self.when](float(v), float(t)):
+            out.collect(Tuple3(ctx.get_current_key(), v, t))
+
+
 class SinkFunction(Function):
     def invoke(self, value, context=None):
         raise NotImplementedError

@@ -20,6 +20,8 @@ positions is lowered onto NativeJoinOp (``_lower_join``); any other join, and ev
 keeps the host plan (tagged union -> keyed window -> co-group function). An interval join with
 positional keys and such a projection is lowered onto NativeIntervalJoinOp
 (``_lower_interval_join``); any other keeps the tagged union -> keyed IntervalJoinOp.
+``a.connect(b).key_by(p, q).process(LookupLatest(..))`` with positional keys is lowered onto
+NativeLookupOp (``_lower_connect``); every other connected function keeps the host operators.
 
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
 (``_lower_topn``): the keyed operator cuts each firing to its top-N candidates on the device.
@@ -295,6 +297,9 @@ def plan(env, sinks):
             continue
         if meta.get("kind") == "interval_join":
             _lower_interval_join(env, t, meta)
+            continue
+        if meta.get("kind") == "connect":
+            _lower_connect(env, t, meta)
             continue
         if meta.get("kind") != "window":
             continue
@@ -924,6 +929,36 @@ def _lower_interval_join(env, t, meta) -> None:
         return NativeIntervalJoinOp(key_pos=kp, val_pos=(lval, rval), layout=layout,
                                     ok_arities=(frozenset(ok[0]), frozenset(ok[1])), lo=lo, hi=hi,
                                     device=device, fallback_factory=fallback)
+
+    t.factory = factory
+    t.meta = dict(t.meta, native=True)
+    meta["columnar"]["on"] = True  # the tag operators let column batches through as they are
+
+
+def _lower_connect(env, t, meta) -> None:
+    """``a.connect(b).key_by(p, q).process(fn)`` -> NativeLookupOp when `fn` is exactly a
+    ``LookupLatest`` (not a subclass, whose methods may differ), both keys are field positions and
+    one rank runs the job. Anything else -- co-maps, co-flat-maps, any other CoProcessFunction,
+    key selectors, several ranks -- keeps the host plan: tagged union -> (keyed) host operator."""
+    from ..runtime.native_ops import NativeLookupOp
+    from . import functions as F
+
+    fn, kp = meta["fn"], meta["key_pos"]
+    comm = getattr(env, "_comm", None)
+    world = comm.world if comm is not None else getattr(env, "world", 1)
+    if meta.get("op") != "process" or type(fn) is not F.LookupLatest or kp is None \
+            or kp[0] is None or kp[1] is None or world > 1:
+        return
+    if isinstance(fn.default, int) and abs(fn.default) > (1 << 53):
+        return  # not a double: the host operator keeps the exact integer
+    fallback = t.factory
+    device = env.config.device
+    val_pos = (fn.value_field, fn.state_field)
+    arities = tuple(range(max(kp[s], val_pos[s]) + 1, 1 << 16) for s in (0, 1))
+
+    def factory():
+        return NativeLookupOp(fn=fn, key_pos=kp, val_pos=val_pos, ok_arities=arities,
+                              device=device, fallback_factory=fallback)
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)

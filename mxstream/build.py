@@ -26,10 +26,11 @@ ARCH = os.environ.get("MXS_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["kernels_hip.hip", "sort_hip.hip", "parse_hip.hip", "vector_hip.hip",
                "check_hip.hip", "rolling_hist_hip.hip", "ingest_hip.hip", "listwin_hip.hip",
-               "format_hip.hip", "exchange_hip.hip", "join_hip.hip", "ijoin_hip.hip"]
+               "format_hip.hip", "exchange_hip.hip", "join_hip.hip", "ijoin_hip.hip",
+               "lookup_hip.hip"]
 CXX_SOURCES = ["kernels_cpu.cpp", "ingest_cpu.cpp", "runtime.cpp", "sessions.cpp", "vector_cpu.cpp",
                "vector_bindings.cpp", "trace.cpp", "check_cpu.cpp", "reader.cpp", "format.cpp", "listwin_cpu.cpp",
-               "listwin_bindings.cpp", "join_cpu.cpp", "join_bindings.cpp", "ijoin_cpu.cpp", "ijoin_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
+               "listwin_bindings.cpp", "join_cpu.cpp", "join_bindings.cpp", "ijoin_cpu.cpp", "ijoin_bindings.cpp", "lookup_cpu.cpp", "lookup_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
                "window_step.cpp", "window_step_bindings.cpp", "bindings.cpp"]
 # roctx ranges (csrc/trace.cpp) come from the ROCm profiler SDK's marker library.
 LINK_LIBS = ["-L/opt/rocm/lib", "-lrocprofiler-sdk-roctx", "-Wl,-rpath,/opt/rocm/lib"]
@@ -142,17 +143,12 @@ def build_sanitize(verbose: bool = False) -> Path:
     return exe
 
 
-SANITIZE_IJOIN_SOURCES = ["ijoin_cpu.cpp", "tests/sanitize_ijoin_main.cpp"]
-
-
-def build_sanitize_ijoin(verbose: bool = False) -> Path:
-    """The interval-join twins (csrc/ijoin_cpu.cpp) + csrc/tests/sanitize_ijoin_main.cpp under
-    AddressSanitizer + UndefinedBehaviorSanitizer: a stand-alone program of its own. Returns the
-    executable's path."""
+def _build_sanitize_program(name: str, sources: list[str], verbose: bool) -> Path:
+    """One stand-alone ASan/UBSan program build/sanitize/<name> from csrc sources."""
     out_dir = ROOT / "build" / "sanitize"
     out_dir.mkdir(parents=True, exist_ok=True)
-    exe = out_dir / "mxs_sanitize_ijoin"
-    srcs = [CSRC / s for s in SANITIZE_IJOIN_SOURCES]
+    exe = out_dir / name
+    srcs = [CSRC / s for s in sources]
     cmd = ["g++", "-std=c++17", *SANITIZE_FLAGS, f"-I{CSRC}", "-I/opt/rocm/include",
            "-D__HIP_PLATFORM_AMD__", *[str(s) for s in srcs], "-o", str(exe)]
     newest = max(s.stat().st_mtime for s in srcs + sorted(CSRC.glob("*.h")))
@@ -163,6 +159,25 @@ def build_sanitize_ijoin(verbose: bool = False) -> Path:
         if verbose:
             print(f"[mxstream.build] built {exe}")
     return exe
+
+
+SANITIZE_IJOIN_SOURCES = ["ijoin_cpu.cpp", "tests/sanitize_ijoin_main.cpp"]
+
+
+def build_sanitize_ijoin(verbose: bool = False) -> Path:
+    """The interval-join twins (csrc/ijoin_cpu.cpp) + csrc/tests/sanitize_ijoin_main.cpp under
+    AddressSanitizer + UndefinedBehaviorSanitizer: a stand-alone program of its own. Returns the
+    executable's path."""
+    return _build_sanitize_program("mxs_sanitize_ijoin", SANITIZE_IJOIN_SOURCES, verbose)
+
+
+SANITIZE_LOOKUP_SOURCES = ["lookup_cpu.cpp", "tests/sanitize_lookup_main.cpp"]
+
+
+def build_sanitize_lookup(verbose: bool = False) -> Path:
+    """The latest-value lookup twins (csrc/lookup_cpu.cpp) + csrc/tests/sanitize_lookup_main.cpp,
+    built the same way. Returns the executable's path."""
+    return _build_sanitize_program("mxs_sanitize_lookup", SANITIZE_LOOKUP_SOURCES, verbose)
 
 
 TSAN_SOURCES = ["tests/tsan_main.cpp"]
@@ -236,6 +251,8 @@ def main(argv: list[str] | None = None) -> int:
         return 0
     if a.sanitize:
         print(build_sanitize(verbose=True))
+        print(build_sanitize_ijoin(verbose=True))
+        print(build_sanitize_lookup(verbose=True))
         return 0
     if a.tsan:
         print(build_tsan(verbose=True))

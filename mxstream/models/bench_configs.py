@@ -971,6 +971,106 @@ def config14(steps: int, warmup: int, batch: int | None = None, keys: int = 100_
     return res
 
 
+def _spread(xs: list) -> dict:
+    """Median, extremes and the 10th / 90th percentile of repeated step times (ms)."""
+    a = np.sort(np.asarray(xs, dtype=np.float64))
+    return {"median": float(np.median(a)), "min": float(a[0]), "max": float(a[-1]),
+            "p10": float(a[int(0.1 * (a.size - 1))]), "p90": float(a[int(round(0.9 * (a.size - 1)))])}
+
+
+def config15(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             when: str | None = ">", zipf: float = 0.0, rules: int = 1 << 12,
+             device: str = "cuda") -> dict:
+    """Keyed latest-value lookup at scale (``samples.connect(rules).key_by(..).process(
+    LookupLatest(..))``): `batch` device-generated samples per step (gen_events, values uniform
+    in [0, 10000)) probe the per-key thresholds of KeyedLookupOperator, fed directly; a rule
+    stream of `rules` updates per step moves thresholds while the job runs. Every key has a
+    threshold before the first step and thresholds are uniform in [9800, 10000), so about 1 % of
+    the samples alert and leave the device as four int64 columns. ``when=None`` keeps every
+    sample (default 0.0): the gather-only path.
+
+    Timed per step, each behind a device synchronise, alternating in the same call: the native
+    step (upsert + probe) and a yardstick that is not the code under test, the torch
+    composition ``table[keys]``, compare, ``nonzero``, four index gathers. The sample generation
+    is outside both windows."""
+    from ..runtime.lookup_operator import KeyedLookupOperator
+
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    default_bits = None if when is not None else 0
+    op = KeyedLookupOperator(when, default_bits, dev)
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    # every key's first threshold
+    ids = torch.arange(keys, dtype=torch.int64, device=dev)
+    first = torch.empty(keys, dtype=torch.int64, device=dev)
+    scratch = torch.empty(keys, dtype=torch.int64, device=dev)
+    K.gen_events(scratch, torch.empty_like(scratch), first, seed=15, stream_id=2, idx0=0,
+                 nkeys=keys, ts_base=t0_event, ts_span=1, disorder=0, val_lo=9_800, val_span=200,
+                 val_f64=True)
+    op.upsert(ids, first)
+    del ids, first, scratch
+    sk, st, sv = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3))
+    rk, rt, rv = (torch.empty(rules, dtype=torch.int64, device=dev) for _ in range(3))
+    state = {"i": 0}
+    native_ms: list[float] = []
+    torch_ms: list[float] = []
+    cmp = {None: None, ">": torch.gt, ">=": torch.ge, "<": torch.lt, "<=": torch.le,
+           "==": torch.eq, "!=": torch.ne}[when]
+
+    def yardstick():
+        rows = op.table[sk]                       # a key at or beyond cap has no rule: none here
+        t = rows[:, 0].view(torch.float64)
+        mask = rows[:, 1] != 0
+        if cmp is not None:
+            mask &= cmp(sv.view(torch.float64), t)
+        idx = mask.nonzero().squeeze(1)
+        return sk[idx], sv[idx], rows[:, 0][idx], st[idx]
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, sv, seed=15, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=0,
+                     val_span=10_000, val_f64=True, zipf=zipf)
+        K.gen_events(rk, rt, rv, seed=15, stream_id=1, idx0=i * rules, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=9_800,
+                     val_span=200, val_f64=True)
+        _sync(dev)
+        t_in = time.perf_counter()
+        op.process(1, rk, rt, rv)
+        out = op.process(0, sk, st, sv)
+        _sync(dev)
+        native_ms.append((time.perf_counter() - t_in) * 1e3)
+        kept = int(out[0][0].numel()) if out else 0
+        t_in = time.perf_counter()
+        ref = yardstick()
+        _sync(dev)
+        torch_ms.append((time.perf_counter() - t_in) * 1e3)
+        if int(ref[0].numel()) != kept or (out and not all(
+                torch.equal(a, b) for a, b in zip(out[0], ref))):
+            raise RuntimeError("config 15: the native probe and the torch composition differ")
+        state["i"] = i + 1
+        return kept
+
+    for _ in range(warmup):
+        step()
+    native_ms.clear()
+    torch_ms.clear()
+    kept = 0
+    for _ in range(steps):
+        kept += step()
+    nat, ref = _spread(native_ms), _spread(torch_ms)
+    return {"config": 15, "metric": "events/sec (keyed latest-value lookup, samples probed)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "native_ms": nat, "torch_ms": ref,
+            "torch_events_per_s": batch / ref["median"] * 1e3,
+            "native_over_torch_time": nat["median"] / ref["median"],
+            "kept_rows": kept, "kept_per_step": kept // max(1, steps),
+            "kept_share": kept / max(1, steps * batch), "when": when, "keys": keys,
+            "samples_per_step": batch, "rules_per_step": rules, "zipf": zipf,
+            "table_rows": op.cap, "steps": steps, "device": str(dev)}
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1253,7 +1353,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1273,6 +1373,8 @@ def main(argv=None) -> int:
                     help="config 5: fraction of events for spilled (long idle) keys")
     ap.add_argument("--lo", type=int, default=-500, help="config 14: lower bound in ms")
     ap.add_argument("--hi", type=int, default=500, help="config 14: upper bound in ms")
+    ap.add_argument("--when", choices=["gt", "none"], default="gt",
+                    help="config 15: sample > threshold (about 1 %% kept) or keep every sample")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None,
@@ -1349,6 +1451,9 @@ def main(argv=None) -> int:
     elif a.config == 14:
         r = config14(a.steps, a.warmup, a.batch, keys=a.keys or 100_000, lo=a.lo, hi=a.hi,
                      zipf=a.zipf, device=a.device)
+    elif a.config == 15:
+        r = config15(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000,
+                     when=">" if a.when == "gt" else None, zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

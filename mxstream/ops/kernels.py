@@ -939,3 +939,146 @@ def ijoin_purge(src, cutoff: int, out: torch.Tensor) -> int:
     m.gpu_ijoin_gather(_p(plan), n, rows, *(_p(c) for c in src), _p(out[0]), _p(out[1]),
                        _p(out[2]), st)
     return rows
+
+
+# ---- keyed latest-value lookup (csrc/mxs_lookup.h) ---------------------------------------------
+
+LOOKUP_WHENS = {None: 0, ">": 1, ">=": 2, "<": 3, "<=": 4, "==": 5, "!=": 6}
+LOOKUP_TILE = 4096
+
+
+def lookup_when(when) -> int:
+    """The comparison's code (csrc LookupWhen); anything but None and the six operators raises."""
+    try:
+        return LOOKUP_WHENS[when]
+    except (KeyError, TypeError):
+        raise ValueError(f"when must be one of '>', '>=', '<', '<=', '==', '!=' or None, "
+                         f"got {when!r}") from None
+
+
+def _lookup_table(table: torch.Tensor) -> int:
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 2 \
+            or table.shape[0] < 1 or not table.is_contiguous() or table.data_ptr() % 16:
+        raise ValueError("lookup: the table must be a contiguous, 16-byte aligned int64 [cap, 2] "
+                         "tensor with cap >= 1")
+    return table.shape[0]
+
+
+def _lookup_cols(cols, names, dev) -> int:
+    n = cols[0].numel()
+    for c, nm in zip(cols, names):
+        _check(c, torch.int64, n, nm, dev)
+        if c.dim() != 1 or c.numel() != n:
+            raise ValueError(f"{nm}: one word per row expected")
+    return n
+
+
+def _lookup_default(default_bits):
+    if default_bits is None:
+        return False, 0
+    d = int(default_bits)
+    if not I64_MIN <= d <= I64_MAX:
+        raise ValueError("lookup: default_bits must be an int64 bit pattern")
+    return True, d
+
+
+def lookup_upsert(table: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor,
+                  max_key: int | None = None) -> None:
+    """Store (vals[i], present) at table[keys[i]] for a batch of rules in arrival order; the last
+    rule of a key wins. Every key must lie in [0, cap) (`max_key`: the batch's largest key when
+    the caller knows it, else one readback of the extremes). GPU: stable radix sort by key, then
+    the row that ends its key's run stores; a one-row batch skips the sort."""
+    dev = table.device
+    cap = _lookup_table(table)
+    n = _lookup_cols((keys, vals), ("keys", "vals"), dev)
+    if n == 0:
+        return
+    if max_key is None or not _is_gpu(table):
+        lo, hi = torch.stack([keys.min(), keys.max()]).tolist()
+    else:
+        lo, hi = 0, int(max_key)
+    if lo < 0 or hi >= cap:
+        raise ValueError(f"lookup_upsert: keys must lie in [0, {cap})")
+    m = load()
+    if not _is_gpu(table):
+        m.cpu_lookup_upsert(_p(keys), _p(vals), n, _p(table), cap)
+        return
+    if n == 1:
+        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
+    m.gpu_lookup_upsert(_p(skeys), _p(perm), _p(vals), n, _p(table), cap, _stream(table))
+
+
+@dataclass
+class LookupMask:
+    """A probed sample batch (``lookup_mask``): what ``lookup_emit`` needs to write the kept rows."""
+    table: torch.Tensor
+    keys: torch.Tensor
+    vals: torch.Tensor
+    has_default: bool
+    default_bits: int
+    words: torch.Tensor     # int64 [ntiles * 64]: one bit per row, 64 words per tile
+    counts: torch.Tensor    # int32 [ntiles]: kept rows per tile
+    offsets: torch.Tensor   # int64 [ntiles]: exclusive scan of counts
+    kept: int
+
+
+def lookup_mask(table: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, when,
+                default_bits=None) -> LookupMask:
+    """Probe the table with a batch of samples: row i is kept when key i has a value in force
+    (its rule's, else the default) and ``vals[i] <when> value`` holds on the two doubles (`when`
+    None: always). Mask words, tile counts, their exclusive scan and the total (one readback)."""
+    dev = table.device
+    cap = _lookup_table(table)
+    n = _lookup_cols((keys, vals), ("keys", "vals"), dev)
+    code = lookup_when(when)
+    has_default, dbits = _lookup_default(default_bits)
+    m = load()
+    ntiles = (n + m.LOOKUP_TILE - 1) // m.LOOKUP_TILE
+    words = torch.empty(max(1, ntiles * m.LOOKUP_WORDS), dtype=torch.int64, device=dev)
+    counts = torch.empty(max(1, ntiles), dtype=torch.int32, device=dev)
+    offsets = torch.empty(max(1, ntiles), dtype=torch.int64, device=dev)
+    meta = torch.zeros(m.LOOKUP_META, dtype=torch.int64, device=dev)
+    cuda = _is_gpu(table)
+    st = _stream(table) if cuda else 0
+    m.lookup_mask(cuda, _p(keys), _p(vals), n, _p(table), cap, code, has_default, dbits,
+                  _p(words), _p(counts), st)
+    m.lookup_scan(cuda, _p(counts), ntiles, _p(offsets), _p(meta), st)
+    kept = int(meta[0].item())
+    return LookupMask(table, keys, vals, has_default, dbits, words[:ntiles * m.LOOKUP_WORDS],
+                      counts[:ntiles], offsets[:ntiles], kept)
+
+
+def lookup_emit(lm: LookupMask, ts: torch.Tensor):
+    """The kept rows of a probed batch, in input order, as four int64 columns: key id, value
+    bits, looked-up bits and timestamp."""
+    dev = lm.table.device
+    n = _lookup_cols((lm.keys, lm.vals, ts), ("keys", "vals", "ts"), dev)
+    out = torch.empty((4, lm.kept), dtype=torch.int64, device=dev)
+    if lm.kept == 0:
+        return out[0], out[1], out[2], out[3]
+    if not 0 <= lm.kept <= n:
+        raise ValueError("lookup_emit: kept rows outside [0, n]")
+    cuda = _is_gpu(lm.table)
+    load().lookup_emit(cuda, _p(lm.keys), _p(lm.vals), _p(ts), n, _p(lm.table), lm.table.shape[0],
+                       lm.has_default, lm.default_bits, _p(lm.words), _p(lm.counts),
+                       _p(lm.offsets), lm.kept, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]),
+                       _stream(lm.table) if cuda else 0)
+    return out[0], out[1], out[2], out[3]
+
+
+def lookup_gather(table: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, ts: torch.Tensor,
+                  default_bits: int):
+    """Every row kept (no comparison, a default): the four columns of ``lookup_emit`` without
+    mask and scan."""
+    dev = table.device
+    cap = _lookup_table(table)
+    n = _lookup_cols((keys, vals, ts), ("keys", "vals", "ts"), dev)
+    _, dbits = _lookup_default(default_bits)
+    out = torch.empty((4, n), dtype=torch.int64, device=dev)
+    cuda = _is_gpu(table)
+    load().lookup_gather(cuda, _p(keys), _p(vals), _p(ts), n, _p(table), cap, dbits, _p(out[0]),
+                         _p(out[1]), _p(out[2]), _p(out[3]), _stream(table) if cuda else 0)
+    return out[0], out[1], out[2], out[3]

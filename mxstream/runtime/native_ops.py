@@ -2223,6 +2223,20 @@ class _NativeTwoSidedOp(Operator):
         return (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray)
                 else x).to(self.op.device)
 
+    def _feed_runs(self, parts) -> list:
+        """Feed the engine maximal runs of one side in arrival order; every chunk of rows it
+        returns (key ids, left bits, right bits, device timestamps) becomes one ColumnBatch."""
+        out, i = [], 0
+        while i < len(parts):
+            j = i
+            while j < len(parts) and parts[j][0] == parts[i][0]:
+                j += 1
+            cols = [torch.cat([self._to_dev(p[c]) for p in parts[i:j]]) for c in (1, 2, 3)]
+            for keys, lv, rv, ts in self.op.process(parts[i][0], *cols):
+                out.append(self._columns(keys, lv, rv, ts.cpu().numpy()))
+            i = j
+        return out
+
     # -- output ---------------------------------------------------------------------------------
     def _columns(self, keys, lv, rv, ts) -> ColumnBatch:
         """One host ColumnBatch in `fn`'s layout from device columns (key ids, left and right
@@ -2373,17 +2387,76 @@ class NativeIntervalJoinOp(_NativeTwoSidedOp):
         if self.wm > LONG_MIN:
             self.op.advance_watermark(self.wm)  # records are late against it from the start
 
-    def _feed(self, parts) -> list:
-        out, i = [], 0
-        while i < len(parts):
-            j = i
-            while j < len(parts) and parts[j][0] == parts[i][0]:
-                j += 1
-            cols = [torch.cat([self._to_dev(p[c]) for p in parts[i:j]]) for c in (1, 2, 3)]
-            for keys, lv, rv, ts in self.op.process(parts[i][0], *cols):
-                out.append(self._columns(keys, lv, rv, ts.cpu().numpy()))
-            i = j
-        return out
+    _feed = _NativeTwoSidedOp._feed_runs
 
     def _on_watermark(self, wm: int) -> list:
         return self.op.advance_watermark(wm)
+
+
+class NativeLookupOp(_NativeTwoSidedOp):
+    """``samples.connect(rules).key_by(p, q).process(LookupLatest(..))`` on the device lookup
+    operator (runtime/lookup_operator.py; planner._lower_connect). Side 0 is the samples, side 1
+    the rules. The pending items are fed as runs of one side in arrival order -- a run of rules
+    is an upsert, a run of samples a probe -- which is exactly what the per-record CoProcessOp
+    computes, in the same output order. Every probe's kept rows come out as one host ColumnBatch
+    ``(key, sample value, value in force)`` with the samples' timestamps. A watermark emits
+    nothing and is forwarded. An integer rule key at or above `dense_limit` is unsupported data
+    like a non-numeric value: the host operator before native state exists, an error afterwards.
+    A default fixes the rules' value kind (int or float): its own."""
+
+    name = "Co-Process(native lookup)"
+
+    def __init__(self, *, fn, dense_limit: int = 1 << 26, **kw):
+        super().__init__(layout=("k", "l", "r"), **kw)
+        self.fn_spec = (fn.value_field, fn.state_field, fn.when, fn.default)
+        self.when, self.default = fn.when, fn.default
+        self.dense_limit = int(dense_limit)
+        if self.default is not None:
+            self.is_float[1] = isinstance(self.default, float)
+
+    def _default_bits(self):
+        if self.default is None:
+            return None
+        return int(np.array([float(self.default)], dtype=np.float64).view(np.int64)[0])
+
+    def _build(self) -> None:
+        from .lookup_operator import KeyedLookupOperator
+
+        self.op = KeyedLookupOperator(self.when, self._default_bits(),
+                                      device=torch.device(self.device),
+                                      dense_limit=self.dense_limit)
+
+    def _dense(self, side: int, cols):
+        kid = cols[0]
+        if side == 1 and not self.str_keys and len(kid) and int(kid.max()) >= self.dense_limit:
+            raise TypeError("rule key beyond the dense table")
+        return cols
+
+    def _recs_columns(self, side: int, recs: list, kinds: list):
+        return self._dense(side, super()._recs_columns(side, recs, kinds))
+
+    def _batch_columns(self, side: int, cb: ColumnBatch, kinds: list):
+        return self._dense(side, super()._batch_columns(side, cb, kinds))
+
+    _feed = _NativeTwoSidedOp._feed_runs
+
+    def _on_watermark(self, wm: int) -> list:
+        return self.op.advance_watermark(wm)
+
+    def snapshot(self) -> dict:
+        snap = super().snapshot()
+        snap["lookup"] = self.fn_spec
+        return snap
+
+    def restore(self, snap: dict) -> None:
+        spec = snap.get("lookup")
+        if "fallback" not in snap and (spec is None or not _same_spec(spec, self.fn_spec)):
+            raise ValueError("checkpoint of a different lookup function")
+        super().restore(snap)
+
+
+def _same_spec(a, b) -> bool:
+    """Function parameters equal, a NaN default equal to itself, 1 and 1.0 apart."""
+    return len(a) == len(b) and all(
+        type(x) is type(y) and (x == y or (isinstance(x, float) and x != x and y != y))
+        for x, y in zip(a, b))

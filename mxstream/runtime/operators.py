@@ -460,6 +460,102 @@ class KeyedProcessOp(KeyedOperator):
         self.wm = snap.get("wm", LONG_MIN)
 
 
+# ---- connected streams (Flink 1.8 ConnectedStreams) ------------------------------------------
+# The input is the tagged union ``(side, value)`` of both streams (runtime/columnar.py TagSideOp).
+
+class CoMapOp(Operator):
+    """CoStreamMap: map1 for the first input's elements, map2 for the second's."""
+
+    name = "Co-Map"
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def open(self, ctx):
+        super().open(ctx)
+        _open_fn(self.fn, ctx)
+
+    def on_record(self, r):
+        side, value = r.value
+        call = self.fn.map1 if side == 0 else self.fn.map2
+        return [Rec(call(value), r.ts, r.subtask)]
+
+
+class CoFlatMapOp(Operator):
+    """CoStreamFlatMap: flat_map1 / flat_map2 with a collector."""
+
+    name = "Co-Flat Map"
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def open(self, ctx):
+        super().open(ctx)
+        _open_fn(self.fn, ctx)
+
+    def on_record(self, r):
+        side, value = r.value
+        col = F.Collector()
+        (self.fn.flat_map1 if side == 0 else self.fn.flat_map2)(value, col)
+        return [Rec(v, r.ts, r.subtask) for v in col.items]
+
+
+class CoProcessOp(KeyedProcessOp):
+    """CoProcessOperator / KeyedCoProcessOperator. Keyed (`key_fn` keys the tagged record by its
+    side's own selector): one keyed state backend and one timer service for both inputs -- state
+    written by process_element2 is what process_element1 of the same key reads; event timers
+    fire when the merged watermark passes them, processing timers in on_processing_time, and
+    on_timer's output carries the timer's timestamp. Not keyed (`key_fn` None): no keyed state
+    and no timers. No element is late."""
+
+    name = "Co-Process"
+
+    def open(self, ctx):
+        if self.key_fn is not None:
+            super().open(ctx)
+            return
+        Operator.open(self, ctx)
+        self.backend = None
+        self.timers = _Timers()  # stays empty: registrations raise
+        _open_fn(self.fn, ctx)
+
+    def on_record(self, r):
+        side, value = r.value
+        ts = None if r.ts == LONG_MIN else r.ts
+        col = F.Collector()
+        if self.key_fn is None:
+            key, sub, timers = None, r.subtask, _NoTimers(self)
+        else:
+            key = F.call_key(self.key_fn, r.value)
+            self.backend.set_current_key(key)
+            self.backend.set_current_namespace(None)
+            sub, timers = self.subtask_of(key), _TimerService(self, key)
+        c = F.CoProcessFunction.Context(ts, timers, self.side, key)
+        (self.fn.process_element1 if side == 0 else self.fn.process_element2)(value, c, col)
+        return [Rec(v, r.ts, sub) for v in col.items]
+
+    def _fire(self, ts, key, domain) -> list:
+        col = F.Collector()
+        self.backend.set_current_key(key)
+        self.backend.set_current_namespace(None)
+        c = F.CoProcessFunction.OnTimerContext(ts, _TimerService(self, key), self.side, domain,
+                                               key)
+        self.fn.on_timer(ts, c, col)
+        sub = self.subtask_of(key)
+        return [Rec(v, ts, sub) for v in col.items]
+
+    def snapshot(self):
+        if self.key_fn is None:
+            return {"wm": self.wm}
+        return super().snapshot()
+
+    def restore(self, snap):
+        if self.key_fn is None:
+            self.wm = snap.get("wm", LONG_MIN)
+            return
+        super().restore(snap)
+
+
 def _sat_add(a: int, b: int) -> int:
     return max(LONG_MIN, min(LONG_MAX, a + b))
 
