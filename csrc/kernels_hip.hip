@@ -1734,10 +1734,29 @@ __device__ __forceinline__ uint32_t pk_cnt(uint64_t p) {
 // DENSE: directly addressed dense key ids (AggPlan.dense_bits): no LDS key table, no probe.
 constexpr uint32_t kAggSliceMin = 131072;  // records per workgroup of a split sub-table
 
-// V (8-byte packed path only, A/B via MXS_AGG_V): bit 0 = eight record loads in flight per
-// thread instead of four; bit 1 = at most 64 VGPRs (launch bounds of eight waves per SIMD), so two
-// 1024-thread workgroups fit one CU when their LDS images do.
-template <int AGG, int RW, bool PK = false, bool DENSE = false, bool DET = false, int V = 0>
+// Lean front end for 8-byte records (LEAN, profiles/window_agg_lean.md): a wave folds whole
+// chunks of kLeanChunk consecutive records, two per lane and 16-byte load, with the next chunk's
+// loads issued before this chunk's LDS atomics. NL 16-byte loads per lane and chunk: a chunk is
+// 128 * NL records.
+template <int NL>
+__device__ __forceinline__ void lean_fetch(uint4 (&b)[NL], const uint4* w, uint32_t chunk) {
+  const uint4* q = w + (size_t)chunk * (64 * NL) + (threadIdx.x & 63u);
+#pragma unroll
+  for (int j = 0; j < NL; ++j) b[j] = q[j * 64];
+}
+
+// Same purpose as pin_rec: the loads stay where they were issued, all in flight together.
+template <int NL>
+__device__ __forceinline__ void lean_pin(uint4 (&b)[NL]) {
+#pragma unroll
+  for (int j = 0; j < NL; ++j)
+    asm volatile("" : "+v"(b[j].x), "+v"(b[j].y), "+v"(b[j].z), "+v"(b[j].w));
+}
+
+// V (8-byte packed path only, A/B via MXS_AGG_V): 2 = at most 64 VGPRs (launch bounds of eight
+// waves per SIMD), so two 1024-thread workgroups fit one CU when their LDS images do.
+template <int AGG, int RW, bool PK = false, bool DENSE = false, bool DET = false, int V = 0,
+          bool LEAN = false>
 __global__ __launch_bounds__(1024, (V & 2) ? 8 : 1) void window_agg_kernel(
     const void* __restrict__ recs, const uint32_t* __restrict__ counts, AggPlan p,
     uint64_t* __restrict__ keys_g, uint64_t* __restrict__ acc_g, uint32_t* __restrict__ cnt_g,
@@ -1816,9 +1835,79 @@ __global__ __launch_bounds__(1024, (V & 2) ? 8 : 1) void window_agg_kernel(
       // This workgroup's share [e_lo, c) of the segment (all of it unless split).
       const uint32_t e_lo = shared_sub ? (uint32_t)((uint64_t)c * slice / nact) : 0u;
       if (shared_sub) c = (uint32_t)((uint64_t)c * (slice + 1) / nact);
+      uint32_t e_gen = e_lo;  // the per-record loop below folds [e_gen, c)
+      if constexpr (LEAN) {
+        static_assert(RW == 1 && !DET, "lean front end: 8-byte records");
+        // Four loads (eight records) per chunk, eight more in flight behind them; the 64-VGPR
+        // build with the LDS probe has registers for two and two (four loads spilled 28 bytes).
+        constexpr int kLeanLoads = (V & 2) && !DENSE ? 2 : 4;
+        constexpr uint32_t kLeanChunk = 128 * kLeanLoads;  // records per wave and chunk
+        // Whole chunks of a 16-byte aligned share: no per-record bounds check, 32-bit decode,
+        // one validity predicate per record. The ragged tail and unaligned shares (an odd
+        // bucket_cap, an odd e_lo of a split) stay with the per-record loop.
+        const uintptr_t a0 = (uintptr_t)((const uint2*)recs + seg0 + e_lo);
+        const uint32_t nch = c > e_lo && !(a0 & 15u) ? (c - e_lo) / kLeanChunk : 0u;
+        const uint32_t nw = blockDim.x >> 6;
+        uint32_t ch = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        if (ch < nch) {
+          const uint4* w = (const uint4*)a0;
+          // Row 0's relative pane clamped to 32 bits: t < 16, so a row outside
+          // [-2^30, 2^30] stays outside [0, npg) after the clamp.
+          const int32_t q0c = q0 > (1 << 30) ? (1 << 30) : q0 < -(1 << 30) ? -(1 << 30) : (int32_t)q0;
+          const uint32_t dmask = p.dense_bits >= 32 ? 0xFFFFFFFFu : (1u << p.dense_bits) - 1u;
+          const uint32_t smask = dmask & mask;
+          auto fold = [&](uint32_t key, uint32_t y) {
+            const uint32_t t = y & 15u;
+            const uint32_t row = sparse ? (uint32_t)__popc(p.pmask & ((1u << t) - 1u)) - (uint32_t)pg0
+                                        : (uint32_t)((int32_t)t - q0c);
+            bool ok = t != kNarrowHoleT && row < (uint32_t)npg;
+            const uint64_t v = (uint64_t)(int64_t)((int32_t)y >> 4);
+            uint32_t s = 0;
+            if constexpr (DENSE) {
+              const bool outside = (key & ~dmask) != 0u;  // id outside the dense key space
+              ovf |= ok && outside;
+              ok = ok && !outside;
+              s = (key * p.dense_mul) & smask;
+            }
+            if (ok) {
+              if constexpr (!DENSE) {
+                s = lds_probe_insert4(skeys, (uint64_t)key, mask, &inserted);
+                if (s == kNoSlot) ovf = true;
+              }
+              if (DENSE || s != kNoSlot) {
+                const uint32_t li = (row << p.cap_log2) + s;
+                if (PK) {
+                  atomicAdd((unsigned long long*)&sacc[li], (unsigned long long)(v + kPkOne));
+                } else {
+                  lds_accumulate<AGG>(&sacc[li], v);
+                  atomicAdd(&scnt[li], 1u);
+                }
+              }
+            }
+          };
+          uint4 cur[kLeanLoads], nxt[kLeanLoads];
+          lean_fetch(cur, w, ch);
+          while (true) {
+            const uint32_t nc = ch + nw;
+            // the last chunk re-reads itself instead of branching around the loads
+            lean_fetch(nxt, w, nc < nch ? nc : ch);
+            lean_pin(cur);
+#pragma unroll
+            for (int j = 0; j < kLeanLoads; ++j) {
+              fold(cur[j].x, cur[j].y);
+              fold(cur[j].z, cur[j].w);
+            }
+            if (nc >= nch) break;
+            ch = nc;
+#pragma unroll
+            for (int j = 0; j < kLeanLoads; ++j) cur[j] = nxt[j];
+          }
+        }
+        e_gen = e_lo + nch * kLeanChunk;
+      }
       // kU independent record loads in flight per thread before the LDS work.
-      constexpr int kU = (V & 1) ? 8 : kAggU;
-      for (uint32_t e0 = e_lo + threadIdx.x; e0 < c; e0 += blockDim.x * kU) {
+      constexpr int kU = kAggU;
+      for (uint32_t e0 = e_gen + threadIdx.x; e0 < c; e0 += blockDim.x * kU) {
         Rec rr[kU];
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
@@ -5753,7 +5842,7 @@ static bool agg_pack_ok(const AggPlan& p) {
          !p.combined && per_wg < 65536;
 }
 
-template <int AGG, int RW, bool PK, bool DENSE, bool DET = false, int V = 0>
+template <int AGG, int RW, bool PK, bool DENSE, bool DET = false, int V = 0, bool LEAN = false>
 static void launch_agg_v(const Rec* recs, const uint32_t* counts, const AggPlan& p,
                          uint64_t* keys_g, uint64_t* acc_g, uint32_t* cnt_g, uint8_t* dirty_g,
                          uint32_t* occ, uint32_t* flags, size_t lds, hipStream_t s) {
@@ -5762,7 +5851,7 @@ static void launch_agg_v(const Rec* recs, const uint32_t* counts, const AggPlan&
   if (lds > kAggDynMax) throw std::runtime_error("window_agg: LDS image exceeds 160 KiB");
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)window_agg_kernel<AGG, RW, PK, DENSE, DET, V>,
+    HIP_CHECK(hipFuncSetAttribute((const void*)window_agg_kernel<AGG, RW, PK, DENSE, DET, V, LEAN>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAggDynMax));
     attr = true;
   }
@@ -5773,9 +5862,25 @@ static void launch_agg_v(const Rec* recs, const uint32_t* counts, const AggPlan&
                         (AGG == AGG_SUM_I64 || AGG == AGG_AVG_I64 || AGG == AGG_COUNT);
   q.split = split_ok && (p.split > 1 || p.split < -1) ? p.split : 1;
   const int nsplit = q.split < 0 ? -q.split : q.split;
-  hipLaunchKernelGGL((window_agg_kernel<AGG, RW, PK, DENSE, DET, V>), dim3(p.nsub * nsplit), dim3(1024),
-                     lds, s, (const void*)recs, counts, q, keys_g, acc_g, cnt_g, dirty_g, occ,
-                     flags);
+  hipLaunchKernelGGL((window_agg_kernel<AGG, RW, PK, DENSE, DET, V, LEAN>), dim3(p.nsub * nsplit),
+                     dim3(1024), lds, s, (const void*)recs, counts, q, keys_g, acc_g, cnt_g,
+                     dirty_g, occ, flags);
+}
+
+// 8-byte records: the lean front end (window_agg_kernel, LEAN) unless MXS_AGG_LEAN=0 (A/B switch,
+// profiles/window_agg_lean.md).
+template <int AGG, bool PK, bool DENSE, int V = 0>
+static void launch_agg_narrow(const Rec* recs, const uint32_t* counts, const AggPlan& p,
+                              uint64_t* keys_g, uint64_t* acc_g, uint32_t* cnt_g,
+                              uint8_t* dirty_g, uint32_t* occ, uint32_t* flags, size_t lds,
+                              hipStream_t s) {
+  const char* e = std::getenv("MXS_AGG_LEAN");  // read per launch: a process can run both sides
+  if (!(e && e[0] == '0'))
+    launch_agg_v<AGG, 1, PK, DENSE, false, V, true>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g,
+                                                    occ, flags, lds, s);
+  else
+    launch_agg_v<AGG, 1, PK, DENSE, false, V, false>(recs, counts, p, keys_g, acc_g, cnt_g,
+                                                     dirty_g, occ, flags, lds, s);
 }
 
 template <int AGG, bool DENSE>
@@ -5799,23 +5904,19 @@ static void launch_agg_d(const Rec* recs, const uint32_t* counts, const AggPlan&
       const size_t lds_pk = keys_lds + (size_t)p.pg * cap * 8 + 16 + list_lds;
       // Default: the 64-VGPR build (V = 2) when two workgroups' LDS images fit a CU -- that is
       // what its register cap buys (hashed 1M-key step 135 -> 119 us); otherwise the default
-      // build (its larger write-back batches). MXS_AGG_V forces a variant (A/B).
+      // build (its larger write-back batches). MXS_AGG_V (0 or 2) forces a variant (A/B).
       static const int v_env = [] {
         const char* e = std::getenv("MXS_AGG_V");
-        return e ? std::atoi(e) & 3 : -1;
+        return e ? std::atoi(e) & 2 : -1;
       }();
       const int v = v_env >= 0 ? v_env : (2 * (lds_pk + 512) <= 160 * 1024 ? 2 : 0);
       if (p.rec_words == 1) {
-        switch (v) {
-          case 1: launch_agg_v<AGG, 1, true, DENSE, false, 1>(recs, counts, p, keys_g, acc_g, cnt_g,
-                                                              dirty_g, occ, flags, lds_pk, s); break;
-          case 2: launch_agg_v<AGG, 1, true, DENSE, false, 2>(recs, counts, p, keys_g, acc_g, cnt_g,
-                                                              dirty_g, occ, flags, lds_pk, s); break;
-          case 3: launch_agg_v<AGG, 1, true, DENSE, false, 3>(recs, counts, p, keys_g, acc_g, cnt_g,
-                                                              dirty_g, occ, flags, lds_pk, s); break;
-          default: launch_agg_v<AGG, 1, true, DENSE>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g,
-                                                     occ, flags, lds_pk, s);
-        }
+        if (v == 2)
+          launch_agg_narrow<AGG, true, DENSE, 2>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g,
+                                                 occ, flags, lds_pk, s);
+        else
+          launch_agg_narrow<AGG, true, DENSE>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g, occ,
+                                              flags, lds_pk, s);
       } else
         launch_agg_v<AGG, 2, true, DENSE>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g, occ,
                                           flags, lds_pk, s);
@@ -5824,8 +5925,8 @@ static void launch_agg_d(const Rec* recs, const uint32_t* counts, const AggPlan&
   }
   const size_t lds = keys_lds + (size_t)p.pg * cap * 12 + 16 + list_lds;
   if (p.rec_words == 1)
-    launch_agg_v<AGG, 1, false, DENSE>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g, occ, flags,
-                                       lds, s);
+    launch_agg_narrow<AGG, false, DENSE>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g, occ,
+                                         flags, lds, s);
   else if (p.rec_words == 2)
     launch_agg_v<AGG, 2, false, DENSE>(recs, counts, p, keys_g, acc_g, cnt_g, dirty_g, occ, flags,
                                        lds, s);
