@@ -1351,6 +1351,7 @@ PYBIND11_MODULE(_mxs_native, m) {
   bind_join(m);
   bind_ijoin(m);
   bind_lookup(m);
+  bind_timeout(m);
   bind_window_tier(m);
   bind_window_control(m);
   bind_window_step(m);

@@ -334,7 +334,10 @@ class KeyedStream(DataStream):
     # -- keyed process / stateful map --
     def process(self, fn) -> SingleOutputStreamOperator:
         key_fn = self.key_fn
-        return self._one_input("KeyedProcess", lambda: O.KeyedProcessOp(key_fn, fn))
+        op = self._one_input("KeyedProcess", lambda: O.KeyedProcessOp(key_fn, fn))
+        op.t.meta = {"kind": "keyed_process", "fn": fn, "key_pos": self.key_pos,
+                     "key_fn": key_fn}
+        return op
 
     def map(self, fn) -> SingleOutputStreamOperator:
         if isinstance(fn, F.RichFunction):  # may use keyed state

@@ -449,6 +449,54 @@ class LookupLatest(CoProcessFunction):
             out.collect(Tuple3(ctx.get_current_key(), v, t))
 
 
+class CountWithTimeout(KeyedProcessFunction):
+    """Per-key element count with an event-time timeout (the ``CountWithTimeoutFunction`` of
+    Flink's ProcessFunction documentation): every element adds one to its key's count, stores its
+    timestamp as the key's `last` (the last arrival, not the largest timestamp) and registers an
+    event-time timer at ``last + timeout``; the timer that still finds ``last + timeout`` equal to
+    its own time -- no element has arrived for `timeout` -- collects
+    ``Tuple3(key, count, last)`` stamped with the timer's time. The state is kept: the count is
+    the key's total, and a later element arms the key again. `timeout` is a positive int
+    (milliseconds) or a ``Time``. A host that has stopped reporting:
+
+        samples.key_by(0).process(CountWithTimeout(Time.seconds(60)))
+
+    The planner runs exactly this class (not a subclass) with a positional key on the device
+    timer operator (runtime/timeout_operator.py); these methods are the exact host
+    implementation used otherwise."""
+
+    def __init__(self, timeout):
+        from .time import Time
+
+        ms = timeout.to_milliseconds() if isinstance(timeout, Time) else timeout
+        if isinstance(ms, bool) or not isinstance(ms, int) or ms <= 0:
+            raise ValueError("CountWithTimeout: timeout is a positive int (milliseconds) or a "
+                             f"Time, got {timeout!r}")
+        self.timeout = ms
+        self.native = ("count_timeout", ms)
+
+    def open(self, parameters=None):
+        from .state import ValueStateDescriptor
+
+        self._state = self.get_runtime_context().get_state(
+            ValueStateDescriptor("count-with-timeout"))
+
+    def process_element(self, value, ctx, out):
+        ts = ctx.timestamp()
+        if ts is None:
+            raise ValueError("CountWithTimeout: a record without an event timestamp")
+        cur = self._state.value()
+        self._state.update(((cur[0] if cur is not None else 0) + 1, ts))
+        ctx.timer_service().register_event_time_timer(ts + self.timeout)
+
+    def on_timer(self, timestamp, ctx, out):
+        from .tuples import Tuple3
+
+        cur = self._state.value()
+        if cur is not None and timestamp == cur[1] + self.timeout:
+            out.collect(Tuple3(ctx.get_current_key(), cur[0], cur[1]))
+
+
 class SinkFunction(Function):
     def invoke(self, value, context=None):
         raise NotImplementedError

@@ -17,6 +17,7 @@ from __future__ import annotations
 import argparse
 import json
 import math
+import os
 import statistics
 import time
 
@@ -1071,6 +1072,97 @@ def config15(steps: int, warmup: int, batch: int | None = None, keys: int = 1_00
             "table_rows": op.cap, "steps": steps, "device": str(dev)}
 
 
+def config16(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             timeout_ms: int = 3_000, zipf: float = 0.0, device: str = "cuda") -> dict:
+    """Keyed event-time timers at scale (``samples.key_by(0).process(CountWithTimeout(..))``):
+    `batch` device-generated samples per 1 s step (gen_events, uniform or zipf keys) feed
+    KeyedTimeoutOperator directly, and every step ends with a watermark at the step's end, which
+    fires the keys that have been silent for `timeout_ms`. The rows leave the device as four int64
+    columns (key id, count, last, deadline) ordered by (deadline, key id).
+
+    Timed per step, each behind a device synchronise, alternating in the same call: the native
+    step (update + firing) and a yardstick that is not the code under test, the torch
+    composition ``scatter_reduce(amax)`` of the arrival index (the key's last row), ``bincount``
+    (the counts), a compare and ``nonzero`` (the firing), gathers and a stable sort by deadline
+    (the output). Both must give the same rows every step. The sample generation is outside both
+    windows."""
+    from ..runtime.timeout_operator import KeyedTimeoutOperator
+
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    op = KeyedTimeoutOperator(timeout_ms, device=dev, dense_limit=max(keys, 1 << 26),
+                              capacity=keys)
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    none = K.TIMEOUT_NONE
+    sk, st, sv = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3))
+    arrival = torch.arange(batch, dtype=torch.int64, device=dev)
+    y_count = torch.zeros(keys, dtype=torch.int64, device=dev)
+    y_last = torch.zeros(keys, dtype=torch.int64, device=dev)
+    y_dead = torch.full((keys,), none, dtype=torch.int64, device=dev)
+    state = {"i": 0}
+    native_ms: list[float] = []
+    torch_ms: list[float] = []
+
+    def yardstick(wm: int):
+        nonlocal y_last, y_dead
+        last_row = torch.full((keys,), -1, dtype=torch.int64, device=dev)
+        last_row.scatter_reduce_(0, sk, arrival, reduce="amax")
+        seen = last_row >= 0
+        y_count.add_(torch.bincount(sk, minlength=keys))
+        y_last = torch.where(seen, st[last_row.clamp_(min=0)], y_last)
+        y_dead = torch.where(seen, y_last + timeout_ms, y_dead)
+        ids = ((y_dead != none) & (y_dead <= wm)).nonzero().squeeze(1)
+        dl = y_dead[ids]
+        y_dead[ids] = none
+        order = torch.sort(dl, stable=True).indices   # ties stay in key order
+        ids = ids[order]
+        return ids, y_count[ids], y_last[ids], dl[order]
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, sv, seed=16, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=0,
+                     val_span=100, zipf=zipf)
+        wm = t0_event + (i + 1) * step_ms
+        _sync(dev)
+        t_in = time.perf_counter()
+        op.process(sk, st)
+        out = op.advance_watermark(wm)
+        _sync(dev)
+        native_ms.append((time.perf_counter() - t_in) * 1e3)
+        fired = int(out[0][0].numel()) if out else 0
+        t_in = time.perf_counter()
+        ref = yardstick(wm)
+        _sync(dev)
+        torch_ms.append((time.perf_counter() - t_in) * 1e3)
+        if int(ref[0].numel()) != fired or (out and not all(
+                torch.equal(a, b) for a, b in zip(out[0], ref))):
+            raise RuntimeError("config 16: the native firing and the torch composition differ")
+        state["i"] = i + 1
+        return fired
+
+    for _ in range(warmup):
+        step()
+    native_ms.clear()
+    torch_ms.clear()
+    fired = 0
+    for _ in range(steps):
+        fired += step()
+    nat, ref = _spread(native_ms), _spread(torch_ms)
+    return {"config": 16, "metric": "events/sec (keyed timers: count, last seen, timeout firing)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "native_ms": nat, "torch_ms": ref,
+            "torch_events_per_s": batch / ref["median"] * 1e3,
+            "native_over_torch_time": nat["median"] / ref["median"],
+            "fired_rows": fired, "fired_per_step": fired // max(1, steps),
+            "fired_share": fired / max(1, steps * keys), "timeout_ms": timeout_ms, "keys": keys,
+            "samples_per_step": batch, "zipf": zipf, "table_rows": op.cap,
+            "tiles": int(op.tile_min.numel()),
+            "tileskip": os.environ.get("MXS_TIMEOUT_TILESKIP", "1") != "0",
+            "steps": steps, "warmup": warmup, "device": str(dev)}
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1353,7 +1445,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1375,6 +1467,8 @@ def main(argv=None) -> int:
     ap.add_argument("--hi", type=int, default=500, help="config 14: upper bound in ms")
     ap.add_argument("--when", choices=["gt", "none"], default="gt",
                     help="config 15: sample > threshold (about 1 %% kept) or keep every sample")
+    ap.add_argument("--timeout-ms", type=int, default=3_000,
+                    help="config 16: a key fires after this much silence (event time)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None,
@@ -1454,6 +1548,9 @@ def main(argv=None) -> int:
     elif a.config == 15:
         r = config15(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000,
                      when=">" if a.when == "gt" else None, zipf=a.zipf, device=a.device)
+    elif a.config == 16:
+        r = config16(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000,
+                     timeout_ms=a.timeout_ms, zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

@@ -1082,3 +1082,133 @@ def lookup_gather(table: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, t
     load().lookup_gather(cuda, _p(keys), _p(vals), _p(ts), n, _p(table), cap, dbits, _p(out[0]),
                          _p(out[1]), _p(out[2]), _p(out[3]), _stream(table) if cuda else 0)
     return out[0], out[1], out[2], out[3]
+
+
+# ---- keyed event-time timers (csrc/mxs_timeout.h) -----------------------------------------------
+
+TIMEOUT_TILE = 4096
+TIMEOUT_NONE = I64_MAX  # deadline of a key that is not armed
+
+
+def timeout_tables(cap: int, device):
+    """Fresh state for `cap` key ids: state int64[cap, 2] of zeros, deadline int64[cap] and
+    tile_min int64[ceil(cap / TIMEOUT_TILE)] of TIMEOUT_NONE."""
+    if cap < 1:
+        raise ValueError("timeout: cap must be >= 1")
+    state = torch.zeros((cap, 2), dtype=torch.int64, device=device)
+    deadline = torch.full((cap,), TIMEOUT_NONE, dtype=torch.int64, device=device)
+    tile_min = torch.full(((cap + TIMEOUT_TILE - 1) // TIMEOUT_TILE,), TIMEOUT_NONE,
+                          dtype=torch.int64, device=device)
+    return state, deadline, tile_min
+
+
+def _timeout_tables(state, deadline, tile_min) -> int:
+    cap = deadline.numel()
+    dev = deadline.device
+    if deadline.dtype != torch.int64 or deadline.dim() != 1 or cap < 1 \
+            or not deadline.is_contiguous() or deadline.data_ptr() % 16:
+        raise ValueError("timeout: deadline must be a contiguous, 16-byte aligned int64 [cap] "
+                         "tensor with cap >= 1")
+    if state is not None and (state.dtype != torch.int64 or state.dim() != 2
+                              or tuple(state.shape) != (cap, 2) or not state.is_contiguous()
+                              or state.data_ptr() % 16 or state.device != dev):
+        raise ValueError("timeout: state must be a contiguous, 16-byte aligned int64 [cap, 2] "
+                         "tensor on the deadlines' device")
+    if tile_min is not None and (tile_min.dtype != torch.int64 or tile_min.dim() != 1
+                                 or tile_min.numel() != (cap + TIMEOUT_TILE - 1) // TIMEOUT_TILE
+                                 or not tile_min.is_contiguous() or tile_min.device != dev):
+        raise ValueError("timeout: tile_min must be a contiguous int64 [ceil(cap / 4096)] tensor "
+                         "on the deadlines' device")
+    return cap
+
+
+def timeout_update(state: torch.Tensor, deadline: torch.Tensor, tile_min: torch.Tensor,
+                   keys: torch.Tensor, ts: torch.Tensor, timeout: int,
+                   bounds: tuple | None = None) -> None:
+    """A batch of elements in arrival order: per key, count += its rows, last = the timestamp of
+    its last row, deadline = last + timeout (armed), tile_min lowered. Every key must lie in
+    [0, cap) and max(ts) + timeout below INT64_MAX (`bounds` = (largest key, largest timestamp)
+    when the caller has read them, else one readback). GPU: stable radix sort by key, then the
+    row that ends its key's run writes; a one-row batch skips the sort."""
+    dev = deadline.device
+    cap = _timeout_tables(state, deadline, tile_min)
+    n = _lookup_cols((keys, ts), ("keys", "ts"), dev)
+    timeout = int(timeout)
+    if not 0 < timeout < I64_MAX:
+        raise ValueError("timeout_update: timeout must be a positive int64")
+    if n == 0:
+        return
+    if bounds is None or not _is_gpu(deadline):
+        lo, hi, tmax = torch.stack([keys.min(), keys.max(), ts.max()]).tolist()
+    else:
+        lo, (hi, tmax) = 0, (int(b) for b in bounds)
+    if lo < 0 or hi >= cap:
+        raise ValueError(f"timeout_update: keys must lie in [0, {cap})")
+    if tmax >= I64_MAX - timeout:
+        raise TypeError("timeout_update: timestamp + timeout reaches INT64_MAX")
+    m = load()
+    if not _is_gpu(deadline):
+        m.cpu_timeout_update(_p(keys), _p(ts), n, timeout, _p(state), _p(deadline), _p(tile_min),
+                             cap)
+        return
+    if n == 1:
+        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
+    m.gpu_timeout_update(_p(skeys), _p(perm), _p(ts), n, timeout, _p(state), _p(deadline),
+                         _p(tile_min), cap, _stream(deadline))
+
+
+@dataclass
+class TimeoutMask:
+    """A scanned firing (``timeout_mask``): what ``timeout_emit`` needs to write the due keys."""
+    words: torch.Tensor     # int64 [ntiles * 64]: one bit per key id (a skipped tile's: unwritten)
+    counts: torch.Tensor    # int32 [ntiles]: due keys per tile
+    offsets: torch.Tensor   # int64 [ntiles]: exclusive scan of counts
+    total: int
+
+
+def timeout_mask(deadline: torch.Tensor, tile_min: torch.Tensor, w: int) -> TimeoutMask:
+    """The keys due at watermark `w` (armed and deadline <= w): mask words and counts per tile of
+    4096 key ids, their exclusive scan and the total (one readback). A tile whose tile_min lies
+    above `w` is not read (MXS_TIMEOUT_TILESKIP=0: every tile is); a scanned tile's tile_min
+    becomes the exact minimum of the deadlines that stay armed."""
+    dev = deadline.device
+    cap = _timeout_tables(None, deadline, tile_min)
+    w = int(w)
+    if not I64_MIN <= w <= I64_MAX:
+        raise ValueError("timeout_mask: the watermark must be an int64")
+    m = load()
+    ntiles = tile_min.numel()
+    words = torch.empty(ntiles * m.TIMEOUT_WORDS, dtype=torch.int64, device=dev)
+    counts = torch.empty(ntiles, dtype=torch.int32, device=dev)
+    offsets = torch.empty(ntiles, dtype=torch.int64, device=dev)
+    meta = torch.zeros(m.LOOKUP_META, dtype=torch.int64, device=dev)
+    cuda = _is_gpu(deadline)
+    st = _stream(deadline) if cuda else 0
+    m.timeout_mask(cuda, _p(deadline), cap, w, _p(tile_min), _p(words), _p(counts), st)
+    m.lookup_scan(cuda, _p(counts), ntiles, _p(offsets), _p(meta), st)
+    return TimeoutMask(words, counts, offsets, int(meta[0].item()))
+
+
+def timeout_emit(state: torch.Tensor, deadline: torch.Tensor, tm: TimeoutMask):
+    """The due keys of a scanned firing in key order as four int64 columns (key id, count, last,
+    deadline); every emitted key is disarmed."""
+    dev = deadline.device
+    cap = _timeout_tables(state, deadline, None)
+    ntiles = (cap + TIMEOUT_TILE - 1) // TIMEOUT_TILE
+    out = torch.empty((4, tm.total), dtype=torch.int64, device=dev)
+    if tm.total == 0:
+        return out[0], out[1], out[2], out[3]
+    if not 0 <= tm.total <= cap or tm.counts.numel() != ntiles or tm.offsets.numel() != ntiles \
+            or tm.words.numel() != ntiles * 64:
+        raise ValueError("timeout_emit: the mask is not of these tables")
+    for t, dt, nm in ((tm.words, torch.int64, "words"), (tm.counts, torch.int32, "counts"),
+                      (tm.offsets, torch.int64, "offsets")):
+        _check(t, dt, t.numel(), nm, dev)
+    cuda = _is_gpu(deadline)
+    load().timeout_emit(cuda, _p(state), _p(deadline), cap, _p(tm.words), _p(tm.counts),
+                        _p(tm.offsets), tm.total, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]),
+                        _stream(deadline) if cuda else 0)
+    return out[0], out[1], out[2], out[3]

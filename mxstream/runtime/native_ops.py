@@ -2455,6 +2455,131 @@ class NativeLookupOp(_NativeTwoSidedOp):
         super().restore(snap)
 
 
+class _NoTimestamp(TypeError):
+    """A record without an event timestamp (unsupported data; the host function's ValueError)."""
+
+
+class NativeTimeoutOp(_NativeTwoSidedOp):
+    """``stream.key_by(p).process(CountWithTimeout(timeout))`` on the device timer operator
+    (runtime/timeout_operator.py; planner._lower_keyed_process). One input: records, host and
+    device column batches are buffered until a watermark or the end of the pass; the watermark
+    feeds them to the engine as one batch in arrival order, fires, and is forwarded. Every
+    firing's rows come out as one host ColumnBatch ``(key, count, last)`` stamped with the
+    deadlines, ascending by (deadline, key id). Keys, the dictionary with its upstream-id
+    tables, the fallback and the pass loop are _NativeTwoSidedOp's. A non-tuple record, a tuple
+    without the key field, a double key, mixed key types, a negative integer key or one at or
+    above `dense_limit`, a record without a timestamp and a timestamp whose deadline would reach
+    INT64_MAX are unsupported data: the host operator before native state exists, an error
+    afterwards."""
+
+    name = "KeyedProcess(native timeout)"
+
+    def __init__(self, *, fn, key_pos: int, device: str, fallback_factory,
+                 dense_limit: int = 1 << 26):
+        super().__init__(key_pos=(key_pos,), val_pos=(), layout=("k",), ok_arities=(),
+                         device=device, fallback_factory=fallback_factory)
+        self.fn_spec = tuple(fn.native)
+        self.timeout = fn.timeout
+        self.key_pos = key_pos
+        self.dense_limit = int(dense_limit)
+
+    def _build(self) -> None:
+        from .timeout_operator import KeyedTimeoutOperator
+
+        self.op = KeyedTimeoutOperator(self.timeout, device=torch.device(self.device),
+                                       dense_limit=self.dense_limit)
+        self.op.wm = self.wm  # a deadline at or below it fires at the next watermark
+
+    def _rec_columns(self, recs: list):
+        kp = self.key_pos
+        kid = np.empty(len(recs), dtype=np.int64)
+        tsa = np.empty(len(recs), dtype=np.int64)
+        for i, r in enumerate(recs):
+            v = r.value
+            if not isinstance(v, tuple) or len(v) <= kp:
+                raise TypeError("no key field")
+            kid[i] = self._key_id(v[kp])
+            tsa[i] = r.ts
+        return kid, tsa
+
+    def _cb_columns(self, cb: ColumnBatch):
+        if isinstance(cb, DeviceColumnBatch) and torch.device(self.device).type != "cuda":
+            cb = cb.host()  # no engine on the batch's device: host columns
+        if cb.scalar or len(cb.kinds) <= self.key_pos:
+            raise TypeError("no key field")
+        if cb.ts is None:
+            raise _NoTimestamp("a batch without event timestamps")
+        return self._batch_keys(cb, self.key_pos), cb.ts[:cb.n]
+
+    def _flush(self) -> list:
+        items, self.pending = self.pending, []
+        if not items:
+            return []
+        try:
+            parts, run = [], []
+            for it in items + [None]:
+                batch = isinstance(it, ColumnBatch)
+                if run and (it is None or batch):
+                    parts.append(self._rec_columns(run))
+                    run = []
+                if it is None:
+                    break
+                if batch:
+                    if it.n:
+                        parts.append(self._cb_columns(it))
+                else:
+                    run.append(it)
+            if not parts:
+                return []
+            dev = torch.device(self.device)
+            to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64))  # noqa: E731
+                                if isinstance(x, np.ndarray) else x).to(dev)
+            keys = torch.cat([to_dev(p[0]) for p in parts])
+            ts = torch.cat([to_dev(p[1]) for p in parts])
+            kmax, tmin, tmax = torch.stack([keys.max(), ts.min(), ts.max()]).tolist()
+            if kmax >= self.dense_limit:
+                raise TypeError("key beyond the dense table")
+            if tmin == LONG_MIN:
+                raise _NoTimestamp("a record without an event timestamp")
+            if tmax >= LONG_MAX - self.timeout:
+                raise TypeError("timestamp + timeout reaches INT64_MAX")
+        except TypeError as e:
+            # Unsupported data for the native path: the exact host operator, while no native
+            # state exists yet.
+            if self.op is not None:
+                if isinstance(e, _NoTimestamp):
+                    raise ValueError("CountWithTimeout: a record without an event "
+                                     "timestamp") from None
+                raise
+            self._to_fallback()
+            return self.fallback.process(expand_columns(items))
+        if self.op is None:
+            self._build()
+        self.op.process(keys, ts)
+        return []
+
+    def _on_watermark(self, wm: int) -> list:
+        out = []
+        for cols in self.op.advance_watermark(wm):
+            keys, count, last, dl = (c.cpu().numpy() for c in cols)
+            out.append(ColumnBatch(int(keys.size), [keys, count, last],
+                                   (FK_STR if self.str_keys else FK_LONG, FK_LONG, FK_LONG),
+                                   self.dict if self.str_keys else None, dl,
+                                   self._subtasks(keys), False))
+        return out
+
+    def snapshot(self) -> dict:
+        snap = super().snapshot()
+        snap["count_timeout"] = self.fn_spec
+        return snap
+
+    def restore(self, snap: dict) -> None:
+        spec = snap.get("count_timeout")
+        if "fallback" not in snap and (spec is None or not _same_spec(spec, self.fn_spec)):
+            raise ValueError("checkpoint of a different timeout function")
+        super().restore(snap)
+
+
 def _same_spec(a, b) -> bool:
     """Function parameters equal, a NaN default equal to itself, 1 and 1.0 apart."""
     return len(a) == len(b) and all(
