@@ -4161,12 +4161,15 @@ __device__ __forceinline__ void sess_clear(SessState& st) {
 __device__ __forceinline__ void sess_store(const SessState& st, SessRec* r) {
 #pragma unroll
   for (int j = 0; j < kSess; ++j) {
+    // A free position (cnt == 0) is stored as all zeroes: a session absorbed by a merge or
+    // dropped by the fire leaves nothing behind, so equal states are equal bit for bit.
+    const bool live = st.cnt[j] != 0;
     SessRec x;
-    x.start = st.start[j];
-    x.end = st.end[j];
-    x.acc = st.acc[j];
+    x.start = live ? st.start[j] : 0;
+    x.end = live ? st.end[j] : 0;
+    x.acc = live ? st.acc[j] : 0ull;
     x.cnt = st.cnt[j];
-    x.flags = st.cnt[j] ? st.flags[j] : 0u;
+    x.flags = live ? st.flags[j] : 0u;
     r[j] = x;
   }
 }

@@ -786,3 +786,153 @@ def test_store_worker_expiry_releases_large_chunks():
     rel = np.concatenate([r["released"] for r in res])
     live = k[cnt != 0]
     assert np.array_equal(rel[:len(live)], live)
+
+
+# ------------------------------------------------ GPU: the fold's non-default paths and knobs
+def _bits(x):
+    return int(np.float64(x).view(np.int64))
+
+
+def _stream_events(seed, n=3000, nkeys=60, span=40_000, float_vals=False):
+    """Roughly ordered events (disorder 400 ms, a straggler every 50th) with negative values."""
+    rng = np.random.default_rng(seed)
+    ts = np.sort(rng.integers(0, span, n)) + rng.integers(-400, 400, n)
+    ts[49::50] -= 1500
+    vals = rng.integers(-500, 500, n)
+    return [(int(k), int(max(t, 0)), _bits(float(v)) if float_vals else int(v))
+            for k, t, v in zip(rng.integers(0, nkeys, n), ts, vals)]
+
+
+def engine_rows(events, gap, bound, lateness, device, batch, agg=K.AGG_SUM_I64, spy=None, **kw):
+    """engine() for any aggregate; spy(op) may wrap the operator before the first batch."""
+    op = KeyedSessionOperator(gap=gap, lateness=lateness, agg=agg, device=device,
+                              max_keys=kw.pop("max_keys", 1 << 10), batch_capacity=max(batch, 64),
+                              ooo_bound=bound, **kw)
+    if spy is not None:
+        spy(op)
+    out = Counter()
+    for i in range(0, len(events) + batch, batch):
+        chunk = events[i:i + batch]
+        k, t, v = (torch.tensor([e[j] for e in chunk], dtype=torch.int64, device=device)
+                   for j in range(3))
+        r = op.process(k, t, v) if chunk else op.finish()
+        out.update(zip(r.keys.tolist(), r.start.tolist(), r.end.tolist(), r.raw.tolist(),
+                       r.counts.tolist()))
+        if not chunk:
+            break
+    return out, op
+
+
+def _same_as_cpu(events, gap, bound, lateness, batch, gpu_kw=None, **kw):
+    a, cpu = engine_rows(events, gap, bound, lateness, "cpu", batch, **kw)
+    b, op = engine_rows(events, gap, bound, lateness, "cuda", batch, **dict(kw, **(gpu_kw or {})))
+    assert a == b and len(a) > 0
+    assert cpu.metrics.num_late_records_dropped == op.metrics.num_late_records_dropped
+    return op
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knob,value", [("_SESSION_SORT", "radix"), ("_SESSION_PAIR", 0),
+                                        ("_REC16", False)])
+def test_gpu_sessions_fold_knobs(knob, value, monkeypatch):
+    """MXS_SESSION_SORT=radix (LDS lookup, radix sort, head-scanning merge), MXS_SESSION_PAIR=0
+    (two output arrays) and MXS_SESSION_REC16=0 (24-byte records from the first step)."""
+    import mxstream.runtime.session_operator as so
+
+    monkeypatch.setattr(so, knob, value)
+    op = _same_as_cpu(_stream_events(21), 100, 100, 300, 500)
+    assert op.rec_w == (3 if knob == "_REC16" else 2)
+
+
+@pytest.mark.gpu
+def test_gpu_sessions_record_widening_mid_stream():
+    """16-byte records until one value outside int32 arrives: that step is redone with 24-byte
+    records (once), and every later step uses them."""
+    events = _stream_events(22)
+    k, t, _ = events[1700]
+    events[1700] = (k, t, 1 << 40)
+    op = _same_as_cpu(events, 100, 100, 300, 500)
+    assert op.metrics.extra["record_widenings"] == 1 and op.rec_w == 3
+
+
+@pytest.mark.gpu
+def test_gpu_sessions_global_lookup_kernel(monkeypatch):
+    """cap_log2 = 13: sub-tables too large for LDS -- the fused lookup-sort declines, and the
+    global-memory lookup kernel and the radix sort run. The geometry stops at 4,096-slot
+    sub-tables, so the test lifts that limit to build two of 8,192."""
+    import mxstream.runtime.geometry as geo
+
+    monkeypatch.setattr(geo, "MAX_CAP_LOG2", 13)
+    monkeypatch.setattr(geo, "MIN_SUBTABLES_NODE", 2)
+    op = _same_as_cpu(_stream_events(23), 100, 100, 300, 500, gpu_kw=dict(sub_table_log2=13))
+    assert (op.nsub, op.cap_log2) == (2, 13)
+
+
+def _spilling_events(seed):
+    rng = np.random.default_rng(seed)
+    n = 6000
+    ts = np.sort(rng.integers(0, 60_000, n))
+    return [(int(k), int(t), int(v)) for k, t, v in
+            zip(rng.integers(0, 1500, n), ts, rng.integers(0, 9, n))]
+
+
+@pytest.mark.gpu
+def test_gpu_sessions_eviction_overflows_staging_rows():
+    """spill_rows = 8: an idle eviction needs more staging rows than there are -- the keys that
+    did not fit stay resident and leave with a later eviction."""
+    rows_needed = []
+
+    def spy(op):
+        evict = op._evict
+
+        def wrapped(**kw):
+            evict(**kw)
+            rows_needed.append(int(op.ctr[7]))
+        op._evict = wrapped
+
+    op = _same_as_cpu(_spilling_events(24), 50, 10_000, 2_000, 600,
+                      gpu_kw=dict(max_load=0.05, idle_spill_ms=1_000, cap_log2=6, spill_rows=8,
+                                  spy=spy))
+    assert max(rows_needed) > 8 and op.metrics.spilled_keys > 8
+
+
+@pytest.mark.gpu
+def test_gpu_sessions_slot_table_rehash(monkeypatch):
+    """Rehash thresholds low enough for the evictions' tombstones to trigger a slot-table rehash
+    in the middle of the run."""
+    import mxstream.runtime.session_operator as so
+
+    monkeypatch.setattr(so, "_REHASH_OCC", 0.02)
+    monkeypatch.setattr(so, "_REHASH_TOMBS", 0.005)
+    op = _same_as_cpu(_spilling_events(25), 50, 10_000, 2_000, 600,
+                      gpu_kw=dict(max_load=0.05, idle_spill_ms=1_000, cap_log2=6))
+    assert op.metrics.rehashes > 0 and op.metrics.spilled_keys > 0
+
+
+@pytest.mark.gpu
+def test_gpu_sessions_hot_key_step():
+    """One step with 1,300 records of one key (a second register slot of the lookup-sort, the
+    wave-per-key merge), 120 of another (just past the 96-record hand-over) and 96 of a third,
+    in runs that split and merge, among ordinary keys."""
+    rng = np.random.default_rng(26)
+    events = []
+    for key, n in ((7, 1300), (8, 120), (9, 96)):
+        ts = np.cumsum(rng.choice([0, 1, 30, 31, 90], n, p=[0.3, 0.4, 0.2, 0.05, 0.05]))
+        events += [(key, int(t), int(v)) for t, v in zip(ts, rng.integers(-9, 9, n))]
+    events += [(int(k), int(t), 1) for k, t in zip(rng.integers(20, 60, 400),
+                                                   rng.integers(0, 20_000, 400))]
+    events = [events[i] for i in rng.permutation(len(events))]
+    assert len(events) == 1916
+    later = [(int(k), 40_000 + int(t), 2) for k, t in zip(rng.integers(0, 60, 300),
+                                                          np.sort(rng.integers(0, 5_000, 300)))]
+    _same_as_cpu(events + later, 30, 100, 50_000, 1916)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("agg", [K.AGG_MIN_I64, K.AGG_MAX_I64, K.AGG_COUNT, K.AGG_SUM_F64,
+                                 K.AGG_AVG_F64])
+def test_gpu_sessions_other_aggregates(agg):
+    """The other aggregates end to end (float values are integer-valued: sums are exact in any
+    order, so the raw accumulators must be equal bit for bit)."""
+    events = _stream_events(27 + agg, float_vals=agg in K.AGG_IS_F64)
+    _same_as_cpu(events, 100, 100, 300, 500, agg=agg)
