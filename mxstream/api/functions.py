@@ -497,6 +497,74 @@ class CountWithTimeout(KeyedProcessFunction):
             out.collect(Tuple3(ctx.get_current_key(), cur[0], cur[1]))
 
 
+class SustainedAlert(KeyedProcessFunction):
+    """A condition that has held for a duration (the ``for:`` of a Prometheus alerting rule):
+    ``value[field] <when> threshold`` is evaluated for every element of a key, in arrival order.
+    The first element of an uninterrupted run of breaching elements stamps the run's `since`;
+    the first element of the run with ``ts - since >= for_`` collects
+    ``Tuple4(key, 1, since, value[field])``, once per run; the first element that does not breach
+    after that collects ``Tuple4(key, 0, since, value[field])`` and closes the run. A run that
+    ends before it fired leaves no trace. Output records carry their element's timestamp; there
+    are no timers. `when` is one of ``">", ">=", "<", "<=", "==", "!="``; values are int or float
+    (not bool) and compare as Java compares doubles (a NaN on either side is false for every
+    operator but ``!=``). `for_` is an int >= 0 (milliseconds) or a ``Time``; 0 reports every
+    run at its first element. A host that has been above 90 % for five minutes:
+
+        samples.key_by(0).process(SustainedAlert(2, ">", 90.0, Time.minutes(5)))
+
+    The planner runs exactly this class (not a subclass) with a positional key on the device
+    operator (runtime/sustain_operator.py); these methods are the exact host implementation used
+    otherwise."""
+
+    def __init__(self, field: int, when: str, threshold, for_):
+        from .time import Time
+
+        if isinstance(field, bool) or not isinstance(field, int) or field < 0:
+            raise ValueError(f"SustainedAlert: field is a non-negative int, got {field!r}")
+        if not isinstance(when, str) or when not in _LOOKUP_WHENS:
+            raise ValueError("SustainedAlert: when must be one of '>', '>=', '<', '<=', '==', "
+                             f"'!=', got {when!r}")
+        self._number(threshold, "threshold")
+        ms = for_.to_milliseconds() if isinstance(for_, Time) else for_
+        if isinstance(ms, bool) or not isinstance(ms, int) or ms < 0:
+            raise ValueError("SustainedAlert: for_ is an int >= 0 (milliseconds) or a Time, "
+                             f"got {for_!r}")
+        self.field, self.when, self.threshold, self.for_ms = field, when, threshold, ms
+        self.native = ("sustained", field, when, threshold, ms)
+
+    @staticmethod
+    def _number(x, what: str):
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise TypeError(f"SustainedAlert: {what} must be an int or a float, got {x!r}")
+        return x
+
+    def open(self, parameters=None):
+        from .state import ValueStateDescriptor
+
+        self._state = self.get_runtime_context().get_state(
+            ValueStateDescriptor("sustained-alert"))
+
+    def process_element(self, value, ctx, out):
+        from .tuples import Tuple4
+
+        ts = ctx.timestamp()
+        if ts is None:
+            raise ValueError("SustainedAlert: a record without an event timestamp")
+        v = self._number(value[self.field], "the element's value")
+        cur = self._state.value()
+        # Python compares an int with a float exactly; Java compares the two doubles
+        if _LOOKUP_WHENS[self.when](float(v), float(self.threshold)):
+            since, firing = cur if cur is not None else (ts, False)
+            if not firing and ts - since >= self.for_ms:
+                firing = True
+                out.collect(Tuple4(ctx.get_current_key(), 1, since, v))
+            self._state.update((since, firing))
+        else:
+            if cur is not None and cur[1]:
+                out.collect(Tuple4(ctx.get_current_key(), 0, cur[0], v))
+            self._state.clear()
+
+
 class SinkFunction(Function):
     def invoke(self, value, context=None):
         raise NotImplementedError

@@ -22,8 +22,9 @@ positional keys and such a projection is lowered onto NativeIntervalJoinOp
 (``_lower_interval_join``); any other keeps the tagged union -> keyed IntervalJoinOp.
 ``a.connect(b).key_by(p, q).process(LookupLatest(..))`` with positional keys is lowered onto
 NativeLookupOp (``_lower_connect``); every other connected function keeps the host operators.
-``key_by(p).process(CountWithTimeout(..))`` is lowered onto NativeTimeoutOp
-(``_lower_keyed_process``); every other keyed process function keeps KeyedProcessOp.
+``key_by(p).process(CountWithTimeout(..))`` is lowered onto NativeTimeoutOp and
+``key_by(p).process(SustainedAlert(..))`` onto NativeSustainOp (``_lower_keyed_process``); every
+other keyed process function keeps KeyedProcessOp.
 
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
 (``_lower_topn``): the keyed operator cuts each firing to its top-N candidates on the device.
@@ -972,22 +973,24 @@ def _lower_connect(env, t, meta) -> None:
 
 def _lower_keyed_process(env, t, meta) -> None:
     """``stream.key_by(p).process(fn)`` -> NativeTimeoutOp when `fn` is exactly a
-    ``CountWithTimeout`` (not a subclass, whose methods may differ), the key is a field position
-    and one rank runs the job. Every other keyed process function, key selectors and several
-    ranks keep the host KeyedProcessOp."""
-    from ..runtime.native_ops import NativeTimeoutOp
+    ``CountWithTimeout`` and -> NativeSustainOp when it is exactly a ``SustainedAlert`` (not a
+    subclass, whose methods may differ), the key is a field position and one rank runs the job.
+    Every other keyed process function, key selectors and several ranks keep the host
+    KeyedProcessOp."""
+    from ..runtime.native_ops import NativeSustainOp, NativeTimeoutOp
     from . import functions as F
 
     fn, kp = meta["fn"], meta["key_pos"]
     comm = getattr(env, "_comm", None)
     world = comm.world if comm is not None else getattr(env, "world", 1)
-    if type(fn) is not F.CountWithTimeout or kp is None or world > 1:
+    native = {F.CountWithTimeout: NativeTimeoutOp, F.SustainedAlert: NativeSustainOp}.get(type(fn))
+    if native is None or kp is None or world > 1:
         return
     fallback = t.factory
     device = env.config.device
 
     def factory():
-        return NativeTimeoutOp(fn=fn, key_pos=kp, device=device, fallback_factory=fallback)
+        return native(fn=fn, key_pos=kp, device=device, fallback_factory=fallback)
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)

@@ -1163,6 +1163,125 @@ def config16(steps: int, warmup: int, batch: int | None = None, keys: int = 1_00
             "steps": steps, "warmup": warmup, "device": str(dev)}
 
 
+def config17(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             for_ms: int = 3_000, zipf: float = 0.0, device: str = "cuda") -> dict:
+    """Sustained-condition alerts at scale (``samples.key_by(0).process(SustainedAlert(2, ">",
+    90, for_))``): `batch` device-generated samples per 1 s step (gen_events, uniform or zipf
+    keys) feed KeyedSustainOperator directly. A key breaches for 10 consecutive steps out of
+    every 1000, at a phase of its own, so about 1 % of the keys are in a breaching run at any
+    time and runs start and end at every step; their values lie in 91..99, all others in 0..89.
+    The transitions leave the device as five int64 columns (key id, code, since, value, ts) in
+    arrival order.
+
+    Timed per step, each behind a device synchronise, alternating in the same call: the native
+    step and a yardstick that is not the code under test, the torch composition of the same
+    result -- a stable sort by key, ``cummax`` of the stretch starts and (stretch id, timestamp)
+    for the run starts and their largest timestamp so far, gathers of the keys' carried state,
+    compares, ``nonzero`` and a sort of the kept rows by arrival. Both must give the same rows
+    every step, and the same table at the end. The sample generation is outside both windows."""
+    from ..runtime.sustain_operator import KeyedSustainOperator
+
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    thr = 90
+    op = KeyedSustainOperator(">", thr, for_ms, device=dev, dense_limit=max(keys, 1 << 26),
+                              capacity=keys)
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    none = K.SUSTAIN_NONE
+    shift = 1 << 11  # > the timestamps' span within a step
+    sk, st, sv = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3))
+    pos = torch.arange(batch, dtype=torch.int64, device=dev)
+    y_state = K.sustain_table(keys, dev)
+    state = {"i": 0}
+    native_ms: list[float] = []
+    torch_ms: list[float] = []
+
+    def shifted(x, fill):
+        out = torch.empty_like(x)
+        out[0] = fill
+        out[1:] = x[:-1]
+        return out
+
+    def yardstick():
+        order = torch.sort(sk, stable=True).indices
+        k, t, v = sk[order], st[order], sv[order]
+        b = v.to(torch.float64) > float(thr)
+        head = shifted(k, -1) != k
+        tail = torch.ones_like(head)
+        tail[:-1] = head[1:]
+        cs, cf = y_state[k, 0], y_state[k, 1] != 0   # the key's state before the batch
+        # a stretch starts at its key's first row and behind every non-breach
+        start = head | ~shifted(b, False)
+        sidx = torch.cummax(torch.where(start, pos, 0), 0).values
+        carried = head[sidx] & (cs != none)
+        since = torch.where(carried, cs, t[sidx])
+        sid = torch.cumsum(start, 0) * shift
+        tmin = t.min()
+        tmax = torch.cummax(sid + (t - tmin), 0).values - sid + tmin
+        fin = b & ((carried & cf) | (tmax - since >= for_ms))
+        fbefore = torch.where(head, cf, shifted(fin, False))
+        sbefore = torch.where(head, cs, shifted(since, 0))
+        fire = fin & ~fbefore
+        idx = (fire | (~b & fbefore)).nonzero().squeeze(1)
+        by_arrival = torch.sort(order[idx]).indices
+        idx = idx[by_arrival]
+        code = fire[idx]
+        rows = (k[idx], code.to(torch.int64), torch.where(code, since[idx], sbefore[idx]), v[idx],
+                t[idx])
+        kt = k[tail]
+        y_state[kt, 0] = torch.where(b[tail], since[tail], none)
+        y_state[kt, 1] = fin[tail].to(torch.int64)
+        return rows
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, sv, seed=17, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=0,
+                     val_span=100, zipf=zipf)
+        breach = (sk * 2_654_435_761 + i) % 1_000 < 10
+        sv.copy_(torch.where(breach, 91 + sv % 9, sv % 90))
+        _sync(dev)
+        t_in = time.perf_counter()
+        out = op.process(sk, sv, st, is_float=False)
+        _sync(dev)
+        native_ms.append((time.perf_counter() - t_in) * 1e3)
+        rows = int(out[0][0].numel()) if out else 0
+        t_in = time.perf_counter()
+        ref = yardstick()
+        _sync(dev)
+        torch_ms.append((time.perf_counter() - t_in) * 1e3)
+        if int(ref[0].numel()) != rows or (out and not all(
+                torch.equal(a, b) for a, b in zip(out[0], ref))):
+            raise RuntimeError("config 17: the native rows and the torch composition differ")
+        state["i"] = i + 1
+        return rows, int(ref[1].sum()) if rows else 0
+
+    for _ in range(warmup):
+        step()
+    native_ms.clear()
+    torch_ms.clear()
+    rows = fired = 0
+    for _ in range(steps):
+        r, f = step()
+        rows, fired = rows + r, fired + f
+    if not torch.equal(op.state[:keys], y_state):
+        raise RuntimeError("config 17: the native table and the torch composition differ")
+    open_runs = int((y_state[:, 0] != none).sum())
+    nat, ref = _spread(native_ms), _spread(torch_ms)
+    return {"config": 17, "metric": "events/sec (sustained-condition alerts: per-key scan)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "native_ms": nat, "torch_ms": ref,
+            "torch_events_per_s": batch / ref["median"] * 1e3,
+            "native_over_torch_time": nat["median"] / ref["median"],
+            "rows": rows, "rows_per_step": rows // max(1, steps),
+            "fired_per_step": fired // max(1, steps),
+            "resolved_per_step": (rows - fired) // max(1, steps),
+            "open_runs_share": open_runs / keys, "firing_keys": int(y_state[:, 1].sum()),
+            "for_ms": for_ms, "keys": keys, "samples_per_step": batch, "zipf": zipf,
+            "table_rows": op.cap, "steps": steps, "warmup": warmup, "device": str(dev)}
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1445,7 +1564,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1469,6 +1588,8 @@ def main(argv=None) -> int:
                     help="config 15: sample > threshold (about 1 %% kept) or keep every sample")
     ap.add_argument("--timeout-ms", type=int, default=3_000,
                     help="config 16: a key fires after this much silence (event time)")
+    ap.add_argument("--for-ms", type=int, default=3_000,
+                    help="config 17: a key is reported once its condition has held this long")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None,
@@ -1551,6 +1672,9 @@ def main(argv=None) -> int:
     elif a.config == 16:
         r = config16(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000,
                      timeout_ms=a.timeout_ms, zipf=a.zipf, device=a.device)
+    elif a.config == 17:
+        r = config17(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, for_ms=a.for_ms,
+                     zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

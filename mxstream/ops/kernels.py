@@ -1212,3 +1212,85 @@ def timeout_emit(state: torch.Tensor, deadline: torch.Tensor, tm: TimeoutMask):
                         _p(tm.offsets), tm.total, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]),
                         _stream(deadline) if cuda else 0)
     return out[0], out[1], out[2], out[3]
+
+
+# ---- sustained-condition alerts (csrc/mxs_sustain.h) --------------------------------------------
+
+SUSTAIN_NONE = I64_MIN        # `since` of a key without an open run
+SUSTAIN_TS_LIMIT = 1 << 62    # |ts| must stay below it: ts - since cannot overflow
+SUSTAIN_LONG, SUSTAIN_DOUBLE = 0, 1
+
+
+def sustain_table(cap: int, device) -> torch.Tensor:
+    """Fresh state for `cap` key ids: int64[cap, 2], every row (SUSTAIN_NONE, 0)."""
+    if cap < 1:
+        raise ValueError("sustain: cap must be >= 1")
+    state = torch.zeros((cap, 2), dtype=torch.int64, device=device)
+    state[:, 0] = SUSTAIN_NONE
+    return state
+
+
+def sustain_update(state: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, ts: torch.Tensor,
+                   *, kind: int, when, threshold_bits: int, for_ms: int,
+                   bounds: tuple | None = None):
+    """A batch of elements in arrival order (key ids, value bits of `kind`, timestamps) against
+    the rule ``value <when> threshold`` held for `for_ms`: the table is updated and the batch's
+    transitions come back in arrival order as five int64 columns (key id, code 1 = fired /
+    0 = resolved, since, value bits, ts). Every key must lie in [0, cap) and every timestamp
+    strictly inside (-2**62, 2**62) (`bounds` = (largest key, smallest and largest timestamp)
+    when the caller has read them, else one readback). GPU: stable radix sort by key, one
+    segmented wave scan, the rows' count read back, a radix sort of the rows by arrival index; a
+    one-row batch skips the first sort."""
+    dev = state.device
+    cap = _lookup_table(state)
+    n = _lookup_cols((keys, vals, ts), ("keys", "vals", "ts"), dev)
+    code = lookup_when(when)
+    if code == 0:
+        raise ValueError("sustain_update: a comparison is required")
+    if kind not in (SUSTAIN_LONG, SUSTAIN_DOUBLE):
+        raise ValueError("sustain_update: kind must be SUSTAIN_LONG or SUSTAIN_DOUBLE")
+    for_ms, tbits = int(for_ms), int(threshold_bits)
+    if not 0 <= for_ms <= I64_MAX:
+        raise ValueError("sustain_update: for_ms must be a non-negative int64")
+    if not I64_MIN <= tbits <= I64_MAX:
+        raise ValueError("sustain_update: threshold_bits must be an int64 bit pattern")
+    if n >= 1 << 31:
+        raise ValueError("sustain_update: at most 2**31 - 1 rows per batch")
+    out = torch.empty((5, n), dtype=torch.int64, device=dev)
+    if n == 0:
+        return tuple(out[c] for c in range(5))
+    if bounds is None or not _is_gpu(state):
+        lo, hi, tmin, tmax = torch.stack([keys.min(), keys.max(), ts.min(), ts.max()]).tolist()
+    else:
+        lo, (hi, tmin, tmax) = 0, (int(b) for b in bounds)
+    if lo < 0 or hi >= cap:
+        raise ValueError(f"sustain_update: keys must lie in [0, {cap})")
+    if tmin <= -SUSTAIN_TS_LIMIT or tmax >= SUSTAIN_TS_LIMIT:
+        raise TypeError("sustain_update: a timestamp at or beyond 2**62")
+    m = load()
+    if not _is_gpu(state):
+        rows = m.cpu_sustain_update(_p(keys), _p(vals), _p(ts), n, kind, code, tbits, for_ms,
+                                    _p(state), cap, *(_p(out[c]) for c in range(5)))
+        return tuple(out[c, :rows] for c in range(5))
+    st = _stream(state)
+    if n == 1:
+        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
+    scratch = torch.empty((2, n), dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    m.gpu_sustain_scan(_p(skeys), _p(perm), _p(vals), _p(ts), n, kind, code, tbits, for_ms,
+                       _p(state), cap, _p(scratch[0]), _p(scratch[1]), _p(count), st)
+    rows = int(count.item())  # the only readback
+    if not 0 <= rows <= n:
+        raise RuntimeError("sustain_update: more transitions than rows")
+    if rows == 0:
+        return tuple(out[c, :0] for c in range(5))
+    # Arrival order: the tags are ``arrival << 1 | code``, one per element at most.
+    tags, since = scratch[0, :rows], scratch[1, :rows]
+    if rows > 1:
+        tags, since = sort_pairs(tags, since, bits=(n - 1).bit_length() + 1)
+    m.gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
+                         *(_p(out[c]) for c in range(5)), st)
+    return tuple(out[c, :rows] for c in range(5))

@@ -2580,6 +2580,159 @@ class NativeTimeoutOp(_NativeTwoSidedOp):
         super().restore(snap)
 
 
+class NativeSustainOp(_NativeTwoSidedOp):
+    """``stream.key_by(p).process(SustainedAlert(field, when, threshold, for_))`` on the device
+    operator (runtime/sustain_operator.py; planner._lower_keyed_process). One input: records,
+    host and device column batches are buffered until a watermark or the end of the pass and
+    then fed to the engine as one batch in arrival order; its transitions come out as one host
+    ColumnBatch ``(key, code, since, value)`` with the samples' timestamps, in arrival order,
+    before the watermark is forwarded. The value column is all longs (carried as they are) or
+    all doubles. A non-tuple record, a tuple without the key or the value field, a value that is
+    no int or float, values of both kinds, a double key, mixed key types, a negative integer key
+    or one at or above `dense_limit`, a record without a timestamp and a timestamp at or beyond
+    2**62 are unsupported data: the host operator before native state exists, an error
+    afterwards."""
+
+    name = "KeyedProcess(native sustained)"
+
+    def __init__(self, *, fn, key_pos: int, device: str, fallback_factory,
+                 dense_limit: int = 1 << 26):
+        super().__init__(key_pos=(key_pos,), val_pos=(fn.field,), layout=("k",), ok_arities=(),
+                         device=device, fallback_factory=fallback_factory)
+        self.fn_spec = tuple(fn.native)
+        self.when, self.threshold, self.for_ms = fn.when, fn.threshold, fn.for_ms
+        self.key_pos, self.val_pos = key_pos, fn.field
+        self.dense_limit = int(dense_limit)
+
+    def _build(self) -> None:
+        from .sustain_operator import KeyedSustainOperator
+
+        self.op = KeyedSustainOperator(self.when, self.threshold, self.for_ms,
+                                       device=torch.device(self.device),
+                                       dense_limit=self.dense_limit)
+
+    def _rec_columns(self, recs: list, kinds: list):
+        kp, vp = self.key_pos, self.val_pos
+        n = len(recs)
+        kid = np.empty(n, dtype=np.int64)
+        tsa = np.empty(n, dtype=np.int64)
+        v0 = recs[0].value
+        if not isinstance(v0, tuple) or len(v0) <= vp or isinstance(v0[vp], bool) \
+                or not isinstance(v0[vp], (int, float)):
+            raise TypeError("no numeric value field")
+        is_float = isinstance(v0[vp], float)
+        self._kind(0, is_float, kinds)
+        vv = np.empty(n, dtype=np.float64 if is_float else np.int64)
+        for i, r in enumerate(recs):
+            v = r.value
+            if not isinstance(v, tuple) or len(v) <= max(kp, vp):
+                raise TypeError("no key or value field")
+            x = v[vp]
+            if isinstance(x, bool) or not isinstance(x, (int, float)) \
+                    or isinstance(x, float) != is_float:
+                raise TypeError("mixed value types")
+            if r.ts is None:
+                raise _NoTimestamp("a record without an event timestamp")
+            kid[i] = self._key_id(v[kp])
+            tsa[i] = r.ts
+            try:
+                vv[i] = x
+            except OverflowError:
+                raise TypeError("an integer beyond int64") from None
+        return kid, tsa, vv.view(np.int64)
+
+    def _cb_columns(self, cb: ColumnBatch, kinds: list):
+        kp, vp = self.key_pos, self.val_pos
+        if isinstance(cb, DeviceColumnBatch) and torch.device(self.device).type != "cuda":
+            cb = cb.host()  # no engine on the batch's device: host columns
+        if cb.scalar or len(cb.kinds) <= max(kp, vp):
+            raise TypeError("no key or value field")
+        if cb.kinds[vp] not in (FK_LONG, FK_DOUBLE):
+            raise TypeError("value column not numeric")
+        if cb.ts is None:
+            raise _NoTimestamp("a batch without event timestamps")
+        is_float = cb.kinds[vp] == FK_DOUBLE
+        self._kind(0, is_float, kinds)
+        col = cb.cols[vp][:cb.n]
+        if isinstance(cb, DeviceColumnBatch):
+            bits = (col.to(torch.float64).contiguous().view(torch.int64) if is_float
+                    else col.to(torch.int64))
+        else:
+            bits = np.ascontiguousarray(col, dtype=np.float64 if is_float else np.int64) \
+                .view(np.int64)
+        return self._batch_keys(cb, kp), cb.ts[:cb.n], bits
+
+    def _flush(self) -> list:
+        items, self.pending = self.pending, []
+        if not items:
+            return []
+        kinds = list(self.is_float)
+        try:
+            parts, run = [], []
+            for it in items + [None]:
+                batch = isinstance(it, ColumnBatch)
+                if run and (it is None or batch):
+                    parts.append(self._rec_columns(run, kinds))
+                    run = []
+                if it is None:
+                    break
+                if batch:
+                    if it.n:
+                        parts.append(self._cb_columns(it, kinds))
+                else:
+                    run.append(it)
+            if not parts:
+                return []
+            dev = torch.device(self.device)
+            to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64))  # noqa: E731
+                                if isinstance(x, np.ndarray) else x).to(dev)
+            keys, ts, bits = (torch.cat([to_dev(p[c]) for p in parts]) for c in range(3))
+            kmax, tmin, tmax = torch.stack([keys.max(), ts.min(), ts.max()]).tolist()
+            if kmax >= self.dense_limit:
+                raise TypeError("key beyond the dense table")
+            if tmin == LONG_MIN:
+                raise _NoTimestamp("a record without an event timestamp")
+            if tmin <= -(1 << 62) or tmax >= 1 << 62:
+                raise TypeError("a timestamp at or beyond 2**62")
+        except TypeError as e:
+            # Unsupported data for the native path: the exact host operator, while no native
+            # state exists yet.
+            if self.op is not None:
+                if isinstance(e, _NoTimestamp):
+                    raise ValueError("SustainedAlert: a record without an event "
+                                     "timestamp") from None
+                raise
+            self._to_fallback()
+            return self.fallback.process(expand_columns(items))
+        self.is_float = kinds
+        if self.op is None:
+            self._build()
+        out = []
+        for cols in self.op.process(keys, bits, ts, is_float=kinds[0]):
+            key, code, since, val, t = (c.cpu().numpy() for c in cols)
+            vals = np.ascontiguousarray(val).view(np.float64) if kinds[0] else val
+            out.append(ColumnBatch(int(key.size), [key, code, since, vals],
+                                   (FK_STR if self.str_keys else FK_LONG, FK_LONG, FK_LONG,
+                                    FK_DOUBLE if kinds[0] else FK_LONG),
+                                   self.dict if self.str_keys else None, t,
+                                   self._subtasks(key), False))
+        return out
+
+    def _on_watermark(self, wm: int) -> list:
+        return self.op.advance_watermark(wm)
+
+    def snapshot(self) -> dict:
+        snap = super().snapshot()
+        snap["sustained"] = self.fn_spec
+        return snap
+
+    def restore(self, snap: dict) -> None:
+        spec = snap.get("sustained")
+        if "fallback" not in snap and (spec is None or not _same_spec(spec, self.fn_spec)):
+            raise ValueError("checkpoint of a different sustained-alert function")
+        super().restore(snap)
+
+
 def _same_spec(a, b) -> bool:
     """Function parameters equal, a NaN default equal to itself, 1 and 1.0 apart."""
     return len(a) == len(b) and all(
