@@ -1353,6 +1353,7 @@ PYBIND11_MODULE(_mxs_native, m) {
   bind_lookup(m);
   bind_timeout(m);
   bind_sustain(m);
+  bind_burst(m);
   bind_window_tier(m);
   bind_window_control(m);
   bind_window_step(m);

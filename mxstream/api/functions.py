@@ -565,6 +565,80 @@ class SustainedAlert(KeyedProcessFunction):
             self._state.clear()
 
 
+class BurstAlert(KeyedProcessFunction):
+    """N breaches within T (the ``times(N).within(T)`` of a CEP pattern, fail2ban's ``maxretry`` /
+    ``findtime``, a flapping host): ``value[field] <when> threshold`` is evaluated for every
+    element of a key, in arrival order, and the timestamps of the key's `times` most recent
+    breaching elements are kept. An element is dense when `times` of them are held and the
+    oldest lies at most `within` before the element's timestamp (a negative difference, disorder,
+    is dense). The first dense breach collects ``Tuple4(key, 1, since, value[field])`` with
+    `since` the oldest held breach, once per burst; the first element after that which is not
+    dense, breaching or not, collects ``Tuple4(key, 0, since, value[field])`` and ends the burst.
+    Output records carry their element's timestamp. There are no timers: a burst that simply
+    stops resolves at the key's next element, whenever that arrives (``CountWithTimeout``
+    reports silence). `when`, the values and the comparison are ``SustainedAlert``'s; `times` is
+    an int >= 2; `within` is an int >= 0 (milliseconds) or a ``Time``, below 2**62. Five errors
+    within ten seconds:
+
+        events.key_by(0).process(BurstAlert(2, ">=", 500, 5, Time.seconds(10)))
+
+    The planner runs exactly this class (not a subclass) with a positional key and
+    ``times <= 16`` on the device operator (runtime/burst_operator.py); these methods are the
+    exact host implementation used otherwise."""
+
+    def __init__(self, field: int, when: str, threshold, times: int, within):
+        from .time import Time
+
+        if isinstance(field, bool) or not isinstance(field, int) or field < 0:
+            raise ValueError(f"BurstAlert: field is a non-negative int, got {field!r}")
+        if not isinstance(when, str) or when not in _LOOKUP_WHENS:
+            raise ValueError("BurstAlert: when must be one of '>', '>=', '<', '<=', '==', "
+                             f"'!=', got {when!r}")
+        self._number(threshold, "threshold")
+        if isinstance(times, bool) or not isinstance(times, int) or times < 2:
+            raise ValueError(f"BurstAlert: times is an int >= 2, got {times!r}")
+        ms = within.to_milliseconds() if isinstance(within, Time) else within
+        if isinstance(ms, bool) or not isinstance(ms, int) or not 0 <= ms < 1 << 62:
+            raise ValueError("BurstAlert: within is an int >= 0 (milliseconds) or a Time, below "
+                             f"2**62, got {within!r}")
+        self.field, self.when, self.threshold = field, when, threshold
+        self.times, self.within_ms = times, ms
+        self.native = ("burst", field, when, threshold, times, ms)
+
+    @staticmethod
+    def _number(x, what: str):
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise TypeError(f"BurstAlert: {what} must be an int or a float, got {x!r}")
+        return x
+
+    def open(self, parameters=None):
+        from .state import ValueStateDescriptor
+
+        self._state = self.get_runtime_context().get_state(ValueStateDescriptor("burst-alert"))
+
+    def process_element(self, value, ctx, out):
+        from .tuples import Tuple4
+
+        ts = ctx.timestamp()
+        if ts is None:
+            raise ValueError("BurstAlert: a record without an event timestamp")
+        v = self._number(value[self.field], "the element's value")
+        recent, since, firing = self._state.value() or ((), None, False)
+        # Python compares an int with a float exactly; Java compares the two doubles
+        breach = _LOOKUP_WHENS[self.when](float(v), float(self.threshold))
+        if breach:
+            recent = (recent + (ts,))[-self.times:]
+        dense = len(recent) == self.times and ts - recent[0] <= self.within_ms
+        if breach and dense and not firing:
+            firing, since = True, recent[0]
+            out.collect(Tuple4(ctx.get_current_key(), 1, since, v))
+        elif not dense and firing:
+            out.collect(Tuple4(ctx.get_current_key(), 0, since, v))
+            firing, since = False, None
+        if recent:
+            self._state.update((recent, since, firing))
+
+
 class SinkFunction(Function):
     def invoke(self, value, context=None):
         raise NotImplementedError

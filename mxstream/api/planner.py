@@ -23,8 +23,9 @@ positional keys and such a projection is lowered onto NativeIntervalJoinOp
 ``a.connect(b).key_by(p, q).process(LookupLatest(..))`` with positional keys is lowered onto
 NativeLookupOp (``_lower_connect``); every other connected function keeps the host operators.
 ``key_by(p).process(CountWithTimeout(..))`` is lowered onto NativeTimeoutOp and
-``key_by(p).process(SustainedAlert(..))`` onto NativeSustainOp (``_lower_keyed_process``); every
-other keyed process function keeps KeyedProcessOp.
+``key_by(p).process(SustainedAlert(..))`` onto NativeSustainOp and
+``key_by(p).process(BurstAlert(..))`` with ``times <= 16`` onto NativeBurstOp
+(``_lower_keyed_process``); every other keyed process function keeps KeyedProcessOp.
 
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
 (``_lower_topn``): the keyed operator cuts each firing to its top-N candidates on the device.
@@ -973,18 +974,23 @@ def _lower_connect(env, t, meta) -> None:
 
 def _lower_keyed_process(env, t, meta) -> None:
     """``stream.key_by(p).process(fn)`` -> NativeTimeoutOp when `fn` is exactly a
-    ``CountWithTimeout`` and -> NativeSustainOp when it is exactly a ``SustainedAlert`` (not a
-    subclass, whose methods may differ), the key is a field position and one rank runs the job.
-    Every other keyed process function, key selectors and several ranks keep the host
-    KeyedProcessOp."""
-    from ..runtime.native_ops import NativeSustainOp, NativeTimeoutOp
+    ``CountWithTimeout``, -> NativeSustainOp when it is exactly a ``SustainedAlert`` and ->
+    NativeBurstOp when it is exactly a ``BurstAlert`` with ``times <= 16``, the width of the
+    engine's per-key ring (not a subclass, whose methods may differ), the key is a field position
+    and one rank runs the job. Every other keyed process function, a ``BurstAlert`` with more
+    `times`, key selectors and several ranks keep the host KeyedProcessOp."""
+    from ..ops.kernels import BURST_MAX_TIMES
+    from ..runtime.native_ops import NativeBurstOp, NativeSustainOp, NativeTimeoutOp
     from . import functions as F
 
     fn, kp = meta["fn"], meta["key_pos"]
     comm = getattr(env, "_comm", None)
     world = comm.world if comm is not None else getattr(env, "world", 1)
-    native = {F.CountWithTimeout: NativeTimeoutOp, F.SustainedAlert: NativeSustainOp}.get(type(fn))
+    native = {F.CountWithTimeout: NativeTimeoutOp, F.SustainedAlert: NativeSustainOp,
+              F.BurstAlert: NativeBurstOp}.get(type(fn))
     if native is None or kp is None or world > 1:
+        return
+    if native is NativeBurstOp and fn.times > BURST_MAX_TIMES:
         return
     fallback = t.factory
     device = env.config.device

@@ -1282,6 +1282,95 @@ def config17(steps: int, warmup: int, batch: int | None = None, keys: int = 1_00
             "table_rows": op.cap, "steps": steps, "warmup": warmup, "device": str(dev)}
 
 
+def config18(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             times: int = 5, within_ms: int = 3_000, zipf: float = 0.0,
+             device: str = "cuda") -> dict:
+    """Burst alerts at scale (``samples.key_by(0).process(BurstAlert(2, ">", 90, times,
+    within))``) on config 17's data: `batch` device-generated samples per 1 s step (gen_events,
+    uniform or zipf keys) feed KeyedBurstOperator directly; a key breaches for 10 consecutive
+    steps out of every 1000, at a phase of its own. The transitions leave the device as five
+    int64 columns (key id, code, since, value, ts) in arrival order.
+
+    Timed per step, each behind a device synchronise, alternating in the same call on the same
+    batch: the burst step and config 17's native step (KeyedSustainOperator, ``for_`` =
+    `within`), which does strictly less per row -- no ring, no look-back. The ratio is reported,
+    not gated. Outside both windows the C++ twin runs every step on host copies: the first three
+    steps' rows and the final ring and rows must equal the device's. The sample generation is
+    outside the windows too."""
+    from ..runtime.burst_operator import KeyedBurstOperator, unpack
+    from ..runtime.sustain_operator import KeyedSustainOperator, threshold_bits
+
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    thr = 90
+    op = KeyedBurstOperator(">", thr, times, within_ms, device=dev,
+                            dense_limit=max(keys, 1 << 26), capacity=keys)
+    sustain = KeyedSustainOperator(">", thr, within_ms, device=dev,
+                                   dense_limit=max(keys, 1 << 26), capacity=keys)
+    twin = K.burst_table(keys, times, "cpu")
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    sk, st, sv = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3))
+    state = {"i": 0}
+    burst_ms: list[float] = []
+    sustain_ms: list[float] = []
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, sv, seed=17, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=0,
+                     val_span=100, zipf=zipf)
+        breach = (sk * 2_654_435_761 + i) % 1_000 < 10
+        sv.copy_(torch.where(breach, 91 + sv % 9, sv % 90))
+        _sync(dev)
+        t_in = time.perf_counter()
+        out = op.process(sk, sv, st, is_float=False)
+        _sync(dev)
+        burst_ms.append((time.perf_counter() - t_in) * 1e3)
+        t_in = time.perf_counter()
+        ref = sustain.process(sk, sv, st, is_float=False)
+        _sync(dev)
+        sustain_ms.append((time.perf_counter() - t_in) * 1e3)
+        want = K.burst_update(twin[0], twin[1], sk.cpu(), sv.cpu(), st.cpu(), kind=K.SUSTAIN_LONG,
+                              when=">", threshold_bits=threshold_bits(thr), within=within_ms)
+        rows = int(out[0][0].numel()) if out else 0
+        if rows != int(want[0].numel()) or (i < 3 and out and not all(
+                torch.equal(a.cpu(), b) for a, b in zip(out[0], want))):
+            raise RuntimeError("config 18: the native rows and the twin's differ")
+        state["i"] = i + 1
+        fired = int(out[0][1].sum()) if out else 0
+        return rows, fired, int(ref[0][0].numel()) if ref else 0
+
+    for _ in range(warmup):
+        step()
+    burst_ms.clear()
+    sustain_ms.clear()
+    rows = fired = sustain_rows = 0
+    for _ in range(steps):
+        r, f, s = step()
+        rows, fired, sustain_rows = rows + r, fired + f, sustain_rows + s
+    if not torch.equal(op.row[:keys].cpu(), twin[1]) or not all(
+            np.array_equal(a, b) for a, b in zip(unpack(op.ring[:keys], op.row[:keys]),
+                                                 unpack(*twin))):
+        raise RuntimeError("config 18: the native state and the twin's differ")
+    held = (twin[1][:, 1] >> K.BURST_HELD_SHIFT) & 0x7f
+    nat, ref = _spread(burst_ms), _spread(sustain_ms)
+    return {"config": 18, "metric": "events/sec (burst alerts: per-key look-back and scan)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "native_ms": nat, "sustain_ms": ref,
+            "sustain_events_per_s": batch / ref["median"] * 1e3,
+            "burst_over_sustain_time": nat["median"] / ref["median"],
+            "rows": rows, "rows_per_step": rows // max(1, steps),
+            "fired_per_step": fired // max(1, steps),
+            "resolved_per_step": (rows - fired) // max(1, steps),
+            "sustain_rows_per_step": sustain_rows // max(1, steps),
+            "keys_with_breaches": int((held > 0).sum()), "keys_with_full_ring":
+            int((held == times).sum()), "firing_keys": int((twin[1][:, 1] & 1).sum()),
+            "times": times, "within_ms": within_ms, "keys": keys, "samples_per_step": batch,
+            "zipf": zipf, "table_rows": op.cap, "steps": steps, "warmup": warmup,
+            "device": str(dev)}
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1564,7 +1653,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1590,6 +1679,10 @@ def main(argv=None) -> int:
                     help="config 16: a key fires after this much silence (event time)")
     ap.add_argument("--for-ms", type=int, default=3_000,
                     help="config 17: a key is reported once its condition has held this long")
+    ap.add_argument("--times", type=int, default=5,
+                    help="config 18: a key is reported at this many breaches")
+    ap.add_argument("--within-ms", type=int, default=3_000,
+                    help="config 18: within this span (event time)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None,
@@ -1675,6 +1768,9 @@ def main(argv=None) -> int:
     elif a.config == 17:
         r = config17(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, for_ms=a.for_ms,
                      zipf=a.zipf, device=a.device)
+    elif a.config == 18:
+        r = config18(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, times=a.times,
+                     within_ms=a.within_ms, zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

@@ -1294,3 +1294,93 @@ def sustain_update(state: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, 
     m.gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
                          *(_p(out[c]) for c in range(5)), st)
     return tuple(out[c, :rows] for c in range(5))
+
+
+# ---- burst alerts (csrc/mxs_burst.h) ------------------------------------------------------------
+
+BURST_MAX_TIMES = 16          # the engine's largest `times`
+BURST_HELD_SHIFT, BURST_POS_SHIFT = 1, 8   # meta = firing | held << 1 | pos << 8
+
+
+def burst_table(cap: int, times: int, device):
+    """Fresh state for `cap` key ids: (ring int64[cap, times], row int64[cap, 2]), all zero: no
+    breach held, not firing."""
+    if cap < 1:
+        raise ValueError("burst: cap must be >= 1")
+    if isinstance(times, bool) or not isinstance(times, int) or not 2 <= times <= BURST_MAX_TIMES:
+        raise ValueError(f"burst: times must be an int in [2, {BURST_MAX_TIMES}]")
+    return (torch.zeros((cap, times), dtype=torch.int64, device=device),
+            torch.zeros((cap, 2), dtype=torch.int64, device=device))
+
+
+def burst_update(ring: torch.Tensor, row: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor,
+                 ts: torch.Tensor, *, kind: int, when, threshold_bits: int, within: int,
+                 bounds: tuple | None = None):
+    """A batch of elements in arrival order (key ids, value bits of `kind`, timestamps) against
+    the rule "`times` breaches of ``value <when> threshold`` within `within` ms" (`times` is the
+    ring's width): ring and row are updated and the batch's transitions come back in arrival
+    order as five int64 columns (key id, code 1 = fired / 0 = resolved, since, value bits, ts).
+    Every key must lie in [0, cap) and every timestamp strictly inside (-2**62, 2**62) (`bounds`
+    = (largest key, smallest and largest timestamp) when the caller has read them, else one
+    readback). GPU: stable radix sort by key, the look-back and one segmented wave scan, the
+    rows' count read back, a radix sort of the rows by arrival index and sustain's gather; a
+    one-row batch skips the first sort."""
+    dev = row.device
+    cap = _lookup_table(row)
+    if ring.dtype != torch.int64 or ring.dim() != 2 or ring.shape[0] != cap \
+            or not 2 <= ring.shape[1] <= BURST_MAX_TIMES or not ring.is_contiguous() \
+            or ring.device != dev or ring.data_ptr() % 8:
+        raise ValueError("burst_update: the ring must be a contiguous int64 [cap, times] tensor "
+                         f"beside the rows, times in [2, {BURST_MAX_TIMES}]")
+    times = ring.shape[1]
+    n = _lookup_cols((keys, vals, ts), ("keys", "vals", "ts"), dev)
+    code = lookup_when(when)
+    if code == 0:
+        raise ValueError("burst_update: a comparison is required")
+    if kind not in (SUSTAIN_LONG, SUSTAIN_DOUBLE):
+        raise ValueError("burst_update: kind must be SUSTAIN_LONG or SUSTAIN_DOUBLE")
+    within, tbits = int(within), int(threshold_bits)
+    if not 0 <= within < SUSTAIN_TS_LIMIT:
+        raise ValueError("burst_update: within must lie in [0, 2**62)")
+    if not I64_MIN <= tbits <= I64_MAX:
+        raise ValueError("burst_update: threshold_bits must be an int64 bit pattern")
+    if n >= 1 << 31:
+        raise ValueError("burst_update: at most 2**31 - 1 rows per batch")
+    out = torch.empty((5, n), dtype=torch.int64, device=dev)
+    if n == 0:
+        return tuple(out[c] for c in range(5))
+    if bounds is None or not _is_gpu(row):
+        lo, hi, tmin, tmax = torch.stack([keys.min(), keys.max(), ts.min(), ts.max()]).tolist()
+    else:
+        lo, (hi, tmin, tmax) = 0, (int(b) for b in bounds)
+    if lo < 0 or hi >= cap:
+        raise ValueError(f"burst_update: keys must lie in [0, {cap})")
+    if tmin <= -SUSTAIN_TS_LIMIT or tmax >= SUSTAIN_TS_LIMIT:
+        raise TypeError("burst_update: a timestamp at or beyond 2**62")
+    m = load()
+    if not _is_gpu(row):
+        rows = m.cpu_burst_update(_p(keys), _p(vals), _p(ts), n, kind, code, tbits, times, within,
+                                  _p(ring), _p(row), cap, *(_p(out[c]) for c in range(5)))
+        return tuple(out[c, :rows] for c in range(5))
+    st = _stream(row)
+    if n == 1:
+        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
+    scratch = torch.empty((2, n), dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    m.gpu_burst_scan(_p(skeys), _p(perm), _p(vals), _p(ts), n, kind, code, tbits, times, within,
+                     _p(ring), _p(row), cap, _p(scratch[0]), _p(scratch[1]), _p(count), st)
+    rows = int(count.item())  # the only readback
+    if not 0 <= rows <= n:
+        raise RuntimeError("burst_update: more transitions than rows")
+    if rows == 0:
+        return tuple(out[c, :0] for c in range(5))
+    # Arrival order: the tags are ``arrival << 1 | code``, one per element at most.
+    tags, since = scratch[0, :rows], scratch[1, :rows]
+    if rows > 1:
+        tags, since = sort_pairs(tags, since, bits=(n - 1).bit_length() + 1)
+    m.gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
+                         *(_p(out[c]) for c in range(5)), st)
+    return tuple(out[c, :rows] for c in range(5))

@@ -2594,15 +2594,21 @@ class NativeSustainOp(_NativeTwoSidedOp):
     afterwards."""
 
     name = "KeyedProcess(native sustained)"
+    # what NativeBurstOp, the same plumbing around another engine, names differently
+    fn_name, snap_key, snap_what = "SustainedAlert", "sustained", "sustained-alert"
 
     def __init__(self, *, fn, key_pos: int, device: str, fallback_factory,
                  dense_limit: int = 1 << 26):
         super().__init__(key_pos=(key_pos,), val_pos=(fn.field,), layout=("k",), ok_arities=(),
                          device=device, fallback_factory=fallback_factory)
         self.fn_spec = tuple(fn.native)
-        self.when, self.threshold, self.for_ms = fn.when, fn.threshold, fn.for_ms
+        self.when, self.threshold = fn.when, fn.threshold
+        self._rule(fn)
         self.key_pos, self.val_pos = key_pos, fn.field
         self.dense_limit = int(dense_limit)
+
+    def _rule(self, fn) -> None:
+        self.for_ms = fn.for_ms
 
     def _build(self) -> None:
         from .sustain_operator import KeyedSustainOperator
@@ -2699,7 +2705,7 @@ class NativeSustainOp(_NativeTwoSidedOp):
             # state exists yet.
             if self.op is not None:
                 if isinstance(e, _NoTimestamp):
-                    raise ValueError("SustainedAlert: a record without an event "
+                    raise ValueError(f"{self.fn_name}: a record without an event "
                                      "timestamp") from None
                 raise
             self._to_fallback()
@@ -2723,14 +2729,34 @@ class NativeSustainOp(_NativeTwoSidedOp):
 
     def snapshot(self) -> dict:
         snap = super().snapshot()
-        snap["sustained"] = self.fn_spec
+        snap[self.snap_key] = self.fn_spec
         return snap
 
     def restore(self, snap: dict) -> None:
-        spec = snap.get("sustained")
+        spec = snap.get(self.snap_key)
         if "fallback" not in snap and (spec is None or not _same_spec(spec, self.fn_spec)):
-            raise ValueError("checkpoint of a different sustained-alert function")
+            raise ValueError(f"checkpoint of a different {self.snap_what} function")
         super().restore(snap)
+
+
+class NativeBurstOp(NativeSustainOp):
+    """``stream.key_by(p).process(BurstAlert(field, when, threshold, times, within))`` on the
+    device operator (runtime/burst_operator.py; planner._lower_keyed_process). Inputs, buffering,
+    the output batches ``(key, code, since, value)``, what counts as unsupported data and what
+    becomes of it are NativeSustainOp's; the engine and the checkpoint's key ("burst") differ."""
+
+    name = "KeyedProcess(native burst)"
+    fn_name, snap_key, snap_what = "BurstAlert", "burst", "burst-alert"
+
+    def _rule(self, fn) -> None:
+        self.times, self.within_ms = fn.times, fn.within_ms
+
+    def _build(self) -> None:
+        from .burst_operator import KeyedBurstOperator
+
+        self.op = KeyedBurstOperator(self.when, self.threshold, self.times, self.within_ms,
+                                     device=torch.device(self.device),
+                                     dense_limit=self.dense_limit)
 
 
 def _same_spec(a, b) -> bool:
