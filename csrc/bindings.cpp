@@ -1354,6 +1354,7 @@ PYBIND11_MODULE(_mxs_native, m) {
   bind_timeout(m);
   bind_sustain(m);
   bind_burst(m);
+  bind_reorder(m);
   bind_window_tier(m);
   bind_window_control(m);
   bind_window_step(m);

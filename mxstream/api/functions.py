@@ -196,8 +196,15 @@ def _acc_fns(fn: AggregateFunction):
 class Collector:
     def __init__(self):
         self.items: list = []
+        self.stamps: dict = {}   # item index -> timestamp, for items collected with one
 
     def collect(self, value):
+        self.items.append(value)
+
+    def collect_at(self, value, ts):
+        """Collect `value` stamped `ts` where the operator would stamp it otherwise (a keyed
+        process function's on_timer: the timer's time)."""
+        self.stamps[len(self.items)] = ts
         self.items.append(value)
 
 
@@ -637,6 +644,96 @@ class BurstAlert(KeyedProcessFunction):
             firing, since = False, None
         if recent:
             self._state.update((recent, since, firing))
+
+
+class _NoTimerService:
+    """What a function wrapped by EventTimeOrdered finds in place of the timer service."""
+
+    def __getattr__(self, name):
+        raise RuntimeError("EventTimeOrdered: the wrapped function may not use the timer service "
+                           f"({name})")
+
+
+class _StampedCollector:
+    """Collects into `out` with the element's timestamp, where `out` can keep one."""
+
+    def __init__(self, out, ts):
+        self._out, self._ts = out, ts
+
+    def collect(self, value):
+        if hasattr(self._out, "collect_at"):
+            self._out.collect_at(value, self._ts)
+        else:
+            self._out.collect(value)
+
+
+class EventTimeOrdered(KeyedProcessFunction):
+    """Event-time order in front of a keyed rule: the elements of a key are buffered, and when
+    the watermark reaches an element's timestamp it is handed to ``fn.process_element`` -- a
+    key's elements in (timestamp, arrival) order, whatever order they arrived in. An element
+    whose timestamp is at or behind the watermark when it arrives is late: it is dropped and
+    counted in ``late_dropped`` (there is no side output). Output records carry their element's
+    timestamp, as the rules' rows do. Per key the result is `fn` applied to the key's elements
+    that are not late, sorted by (timestamp, arrival). `fn` is a ``KeyedProcessFunction`` that
+    does not override ``on_timer`` and does not use the timer service. A rule that must not be
+    fooled by a straggler:
+
+        samples.key_by(0).process(EventTimeOrdered(SustainedAlert(2, ">", 90.0, Time.minutes(5))))
+
+    The planner runs exactly this class around exactly a ``SustainedAlert`` or a ``BurstAlert``
+    (``times <= 16``) with a positional key on the device reorder buffer
+    (runtime/reorder_operator.py) in front of the rule's device operator; these methods are the
+    exact host implementation used otherwise."""
+
+    def __init__(self, fn):
+        if not isinstance(fn, KeyedProcessFunction) \
+                or type(fn).on_timer is not ProcessFunction.on_timer:
+            raise ValueError("EventTimeOrdered: fn is a KeyedProcessFunction that does not "
+                             f"override on_timer, got {fn!r}")
+        self.fn = fn
+        self.late_dropped = 0
+        if hasattr(fn, "native"):
+            self.native = ("event_time_ordered",) + tuple(fn.native)
+
+    def open(self, parameters=None):
+        from .state import ValueStateDescriptor
+
+        ctx = self.get_runtime_context()
+        self.fn.set_runtime_context(ctx)
+        self.fn.open(parameters)
+        # (the key's next arrival number, its buffered (ts, seq, value) entries)
+        self._state = ctx.get_state(ValueStateDescriptor("event-time-ordered"))
+
+    def process_element(self, value, ctx, out):
+        ts = ctx.timestamp()
+        if ts is None:
+            raise ValueError("EventTimeOrdered: a record without an event timestamp")
+        timers = ctx.timer_service()
+        if ts <= timers.current_watermark():
+            self.late_dropped += 1
+            return
+        seq, entries = self._state.value() or (0, [])
+        self._state.update((seq + 1, entries + [(ts, seq, value)]))
+        timers.register_event_time_timer(ts)
+
+    def on_timer(self, timestamp, ctx, out):
+        cur = self._state.value()
+        if cur is None:
+            return
+        seq, entries = cur
+        due = sorted((e for e in entries if e[0] <= timestamp), key=lambda e: e[:2])
+        if not due:
+            return
+        rest = [e for e in entries if e[0] > timestamp]
+        # the arrival counter goes with the buffer: an empty one starts over
+        if rest:
+            self._state.update((seq, rest))
+        else:
+            self._state.clear()
+        key, side = ctx.get_current_key(), getattr(ctx, "_side", None)
+        for ts, _, value in due:
+            c = ProcessFunction.Context(ts, _NoTimerService(), side, key)
+            self.fn.process_element(value, c, _StampedCollector(out, ts))
 
 
 class SinkFunction(Function):

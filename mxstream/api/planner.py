@@ -25,7 +25,8 @@ NativeLookupOp (``_lower_connect``); every other connected function keeps the ho
 ``key_by(p).process(CountWithTimeout(..))`` is lowered onto NativeTimeoutOp and
 ``key_by(p).process(SustainedAlert(..))`` onto NativeSustainOp and
 ``key_by(p).process(BurstAlert(..))`` with ``times <= 16`` onto NativeBurstOp
-(``_lower_keyed_process``); every other keyed process function keeps KeyedProcessOp.
+(``_lower_keyed_process``), each of the last two also under ``EventTimeOrdered(..)``, with the
+device reorder buffer in front; every other keyed process function keeps KeyedProcessOp.
 
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
 (``_lower_topn``): the keyed operator cuts each firing to its top-N candidates on the device.
@@ -978,7 +979,11 @@ def _lower_keyed_process(env, t, meta) -> None:
     NativeBurstOp when it is exactly a ``BurstAlert`` with ``times <= 16``, the width of the
     engine's per-key ring (not a subclass, whose methods may differ), the key is a field position
     and one rank runs the job. Every other keyed process function, a ``BurstAlert`` with more
-    `times`, key selectors and several ranks keep the host KeyedProcessOp."""
+    `times`, key selectors and several ranks keep the host KeyedProcessOp.
+
+    ``EventTimeOrdered(fn)`` (exactly that class) around exactly a ``SustainedAlert`` or a
+    ``BurstAlert`` lowers, under the same conditions, onto the same operators with
+    ``ordered=True``: the device reorder buffer in front of the rule."""
     from ..ops.kernels import BURST_MAX_TIMES
     from ..runtime.native_ops import NativeBurstOp, NativeSustainOp, NativeTimeoutOp
     from . import functions as F
@@ -986,6 +991,13 @@ def _lower_keyed_process(env, t, meta) -> None:
     fn, kp = meta["fn"], meta["key_pos"]
     comm = getattr(env, "_comm", None)
     world = comm.world if comm is not None else getattr(env, "world", 1)
+    kw = {}
+    if type(fn) is F.EventTimeOrdered:
+        # the device reorder buffer in front of the two rules; any other wrapped function keeps
+        # the host wrapper
+        fn, kw = fn.fn, {"ordered": True}
+        if type(fn) not in (F.SustainedAlert, F.BurstAlert):
+            return
     native = {F.CountWithTimeout: NativeTimeoutOp, F.SustainedAlert: NativeSustainOp,
               F.BurstAlert: NativeBurstOp}.get(type(fn))
     if native is None or kp is None or world > 1:
@@ -996,7 +1008,7 @@ def _lower_keyed_process(env, t, meta) -> None:
     device = env.config.device
 
     def factory():
-        return native(fn=fn, key_pos=kp, device=device, fallback_factory=fallback)
+        return native(fn=fn, key_pos=kp, device=device, fallback_factory=fallback, **kw)
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)

@@ -28,10 +28,10 @@ HIP_SOURCES = ["kernels_hip.hip", "sort_hip.hip", "parse_hip.hip", "vector_hip.h
                "check_hip.hip", "rolling_hist_hip.hip", "ingest_hip.hip", "listwin_hip.hip",
                "format_hip.hip", "exchange_hip.hip", "join_hip.hip", "ijoin_hip.hip",
                "lookup_hip.hip", "timeout_hip.hip", "sustain_hip.hip",
-               "burst_hip.hip"]
+               "burst_hip.hip", "reorder_hip.hip"]
 CXX_SOURCES = ["kernels_cpu.cpp", "ingest_cpu.cpp", "runtime.cpp", "sessions.cpp", "vector_cpu.cpp",
                "vector_bindings.cpp", "trace.cpp", "check_cpu.cpp", "reader.cpp", "format.cpp", "listwin_cpu.cpp",
-               "listwin_bindings.cpp", "join_cpu.cpp", "join_bindings.cpp", "ijoin_cpu.cpp", "ijoin_bindings.cpp", "lookup_cpu.cpp", "lookup_bindings.cpp", "timeout_cpu.cpp", "timeout_bindings.cpp", "sustain_cpu.cpp", "sustain_bindings.cpp", "burst_cpu.cpp", "burst_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
+               "listwin_bindings.cpp", "join_cpu.cpp", "join_bindings.cpp", "ijoin_cpu.cpp", "ijoin_bindings.cpp", "lookup_cpu.cpp", "lookup_bindings.cpp", "timeout_cpu.cpp", "timeout_bindings.cpp", "sustain_cpu.cpp", "sustain_bindings.cpp", "burst_cpu.cpp", "burst_bindings.cpp", "reorder_cpu.cpp", "reorder_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
                "window_step.cpp", "window_step_bindings.cpp", "bindings.cpp"]
 # roctx ranges (csrc/trace.cpp) come from the ROCm profiler SDK's marker library.
 LINK_LIBS = ["-L/opt/rocm/lib", "-lrocprofiler-sdk-roctx", "-Wl,-rpath,/opt/rocm/lib"]
@@ -208,6 +208,15 @@ def build_sanitize_burst(verbose: bool = False) -> Path:
     return _build_sanitize_program("mxs_sanitize_burst", SANITIZE_BURST_SOURCES, verbose)
 
 
+SANITIZE_REORDER_SOURCES = ["reorder_cpu.cpp", "tests/sanitize_reorder_main.cpp"]
+
+
+def build_sanitize_reorder(verbose: bool = False) -> Path:
+    """The reorder-buffer twins (csrc/reorder_cpu.cpp) + csrc/tests/sanitize_reorder_main.cpp,
+    built the same way. Returns the executable's path."""
+    return _build_sanitize_program("mxs_sanitize_reorder", SANITIZE_REORDER_SOURCES, verbose)
+
+
 TSAN_SOURCES = ["tests/tsan_main.cpp"]
 TSAN_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=thread", "-pthread"]
 
@@ -284,6 +293,7 @@ def main(argv: list[str] | None = None) -> int:
         print(build_sanitize_timeout(verbose=True))
         print(build_sanitize_sustain(verbose=True))
         print(build_sanitize_burst(verbose=True))
+        print(build_sanitize_reorder(verbose=True))
         return 0
     if a.tsan:
         print(build_tsan(verbose=True))

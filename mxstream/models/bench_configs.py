@@ -1371,6 +1371,109 @@ def config18(steps: int, warmup: int, batch: int | None = None, keys: int = 1_00
             "device": str(dev)}
 
 
+def config19(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             for_ms: int = 3_000, disorder_ms: int = 3_000, zipf: float = 0.0,
+             device: str = "cuda") -> dict:
+    """Event-time order in front of a rule at scale (``samples.key_by(0).process(
+    EventTimeOrdered(SustainedAlert(2, ">", 90, for_)))``) on config 17's data, every timestamp
+    displaced backwards uniformly within `disorder_ms` (0: the stream is in order). Each 1 s step
+    sends the watermark of the step's end minus the disorder, so no row is late and about
+    `disorder_ms` / 1 s steps of rows are buffered at any time.
+
+    Timed per step, each behind a device synchronise, alternating in the same call on the same
+    batch: the ordered step -- EventOrderBuffer.push, release at the watermark and
+    KeyedSustainOperator over the released rows -- and config 17's plain native step, a second
+    KeyedSustainOperator over the batch in arrival order. The ratio is reported, not gated.
+    Outside both windows the C++ twins (buffer and rule) run every step on host copies: the
+    first three steps' rows and the final buffer contents must equal the device's, and every
+    step's row count. The sample generation is outside the windows too."""
+    from ..runtime.reorder_operator import EventOrderBuffer
+    from ..runtime.sustain_operator import KeyedSustainOperator
+
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    thr = 90
+    if disorder_ms < 0:
+        raise ValueError("config 19: --disorder-ms must be >= 0")
+    make = lambda d: KeyedSustainOperator(">", thr, for_ms, device=d,  # noqa: E731
+                                          dense_limit=max(keys, 1 << 26), capacity=keys)
+    buf, rule, plain = EventOrderBuffer(dev, capacity=4 * batch), make(dev), make(dev)
+    tbuf, trule = EventOrderBuffer("cpu", capacity=4 * batch), make("cpu")
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    sk, st, sv = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3))
+    state = {"i": 0}
+    ordered_ms: list[float] = []
+    plain_ms: list[float] = []
+    chunks: list[int] = []
+    buffered: list[int] = []
+    contrib: list[int] = []
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, sv, seed=17, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=disorder_ms,
+                     val_lo=0, val_span=100, zipf=zipf)
+        breach = (sk * 2_654_435_761 + i) % 1_000 < 10
+        sv.copy_(torch.where(breach, 91 + sv % 9, sv % 90))
+        wm = t0_event + (i + 1) * step_ms - 1 - disorder_ms
+        _sync(dev)
+        t_in = time.perf_counter()
+        buf.push(sk, st, sv)
+        cols = buf.release(wm)
+        out = rule.process(cols[0], cols[2], cols[1], is_float=False) if cols is not None else []
+        _sync(dev)
+        ordered_ms.append((time.perf_counter() - t_in) * 1e3)
+        chunks.append(len(buf.chunks))
+        buffered.append(buf.rows_buffered)
+        contrib.append(buf.last_contrib)
+        t_in = time.perf_counter()
+        ref = plain.process(sk, sv, st, is_float=False)
+        _sync(dev)
+        plain_ms.append((time.perf_counter() - t_in) * 1e3)
+        tbuf.push(sk.cpu(), st.cpu(), sv.cpu())
+        tcols = tbuf.release(wm)
+        want = trule.process(tcols[0], tcols[2], tcols[1], is_float=False) \
+            if tcols is not None else []
+        rows = int(out[0][0].numel()) if out else 0
+        if rows != (int(want[0][0].numel()) if want else 0) or (i < 3 and out and not all(
+                torch.equal(a.cpu(), b) for a, b in zip(out[0], want[0]))):
+            raise RuntimeError("config 19: the native rows and the twins' differ")
+        state["i"] = i + 1
+        return rows, int(cols[0].numel()) if cols is not None else 0, \
+            int(ref[0][0].numel()) if ref else 0
+
+    for _ in range(warmup):
+        step()
+    for x in (ordered_ms, plain_ms, chunks, buffered, contrib):
+        x.clear()
+    rows = released = plain_rows = 0
+    for _ in range(steps):
+        r, n, p = step()
+        rows, released, plain_rows = rows + r, released + n, plain_rows + p
+    if buf.metrics != tbuf.metrics or not all(
+            np.array_equal(a, b) for a, b in zip(buf.rows(), tbuf.rows())):
+        raise RuntimeError("config 19: the native buffer and the twin's differ")
+    nat, ref = _spread(ordered_ms), _spread(plain_ms)
+    return {"config": 19, "metric": "events/sec (event-time order in front of sustained alerts)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "ordered_ms": nat, "plain_ms": ref,
+            "plain_events_per_s": batch / ref["median"] * 1e3,
+            "ordered_over_plain_time": nat["median"] / ref["median"],
+            "rows": rows, "rows_per_step": rows // max(1, steps),
+            "plain_rows_per_step": plain_rows // max(1, steps),
+            "released_per_step": released // max(1, steps),
+            "live_chunks": int(np.median(chunks)) if chunks else 0,
+            "buffered_rows": int(np.median(buffered)) if buffered else 0,
+            "contributing_chunks": int(np.median(contrib)) if contrib else 0,
+            "slice_path_steps": sum(c == 1 for c in contrib),
+            "consolidations": buf.consolidations, "arena_rows": buf.cap,
+            "late_dropped": buf.metrics.num_late_records_dropped,
+            "disorder_ms": disorder_ms, "for_ms": for_ms, "keys": keys,
+            "samples_per_step": batch, "zipf": zipf, "steps": steps, "warmup": warmup,
+            "device": str(dev)}
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1653,7 +1756,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1683,6 +1786,9 @@ def main(argv=None) -> int:
                     help="config 18: a key is reported at this many breaches")
     ap.add_argument("--within-ms", type=int, default=3_000,
                     help="config 18: within this span (event time)")
+    ap.add_argument("--disorder-ms", type=int, default=3_000,
+                    help="config 19: timestamps are displaced backwards uniformly within this "
+                         "span, and the watermark runs this far behind (0: an in-order stream)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None,
@@ -1771,6 +1877,9 @@ def main(argv=None) -> int:
     elif a.config == 18:
         r = config18(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, times=a.times,
                      within_ms=a.within_ms, zipf=a.zipf, device=a.device)
+    elif a.config == 19:
+        r = config19(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, for_ms=a.for_ms,
+                     disorder_ms=a.disorder_ms, zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

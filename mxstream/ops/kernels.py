@@ -1384,3 +1384,97 @@ def burst_update(ring: torch.Tensor, row: torch.Tensor, keys: torch.Tensor, vals
     m.gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
                          *(_p(out[c]) for c in range(5)), st)
     return tuple(out[c, :rows] for c in range(5))
+
+
+# ---- event-time reorder buffer (csrc/mxs_reorder.h) ---------------------------------------------
+
+REORDER_TILE = 4096           # output positions a workgroup of the collect owns
+REORDER_MAX_CHUNKS = 1024     # chunks one cut / collect takes
+
+
+def _reorder_ts(ts: torch.Tensor, n_arena: int) -> None:
+    _check(ts, torch.int64, n_arena, "ts", ts.device)
+    if ts.dim() != 1 or n_arena < 0:
+        raise ValueError("reorder: ts must be one int64 column holding the arena's rows")
+
+
+def _reorder_flag(err: torch.Tensor, dev) -> None:
+    _check(err, torch.int64, 1, "err", dev)
+
+
+def reorder_cut(ts: torch.Tensor, n_arena: int, begins, ends, w: int, cut: torch.Tensor) -> None:
+    """Per chunk c, ``cut[c]`` = the first position of the ascending ``ts[begins[c], ends[c])``
+    whose timestamp exceeds `w` (ends[c] when none does). `begins` / `ends` are host lists with
+    0 <= begin <= end <= n_arena; `cut` is an int64 device column of at least as many words,
+    written in place (no readback here)."""
+    dev = ts.device
+    _reorder_ts(ts, n_arena)
+    k = len(begins)
+    if len(ends) != k or not 1 <= k <= REORDER_MAX_CHUNKS:
+        raise ValueError(f"reorder_cut: 1 to {REORDER_MAX_CHUNKS} chunks, one end per begin")
+    if any(not 0 <= b <= e <= n_arena for b, e in zip(begins, ends)):
+        raise ValueError("reorder_cut: a chunk outside the arena")
+    if not I64_MIN <= w <= I64_MAX:
+        raise ValueError("reorder_cut: the watermark must be an int64")
+    _check(cut, torch.int64, k, "cut", dev)
+    tab = torch.tensor([list(begins), list(ends)], dtype=torch.int64).to(dev)
+    m = load()
+    if _is_gpu(ts):
+        m.gpu_reorder_cut(_p(ts), n_arena, _p(tab[0]), _p(tab[1]), k, w, _p(cut), _stream(ts))
+    else:
+        m.cpu_reorder_cut(_p(ts), n_arena, _p(tab[0]), _p(tab[1]), k, w, _p(cut))
+
+
+def reorder_collect(ts: torch.Tensor, n_arena: int, begins, counts, lo: int, err: torch.Tensor):
+    """The rows ``[begins[c], begins[c] + counts[c])`` of every chunk, in chunk order, as two
+    int64 columns (``ts - lo``, arena index): the pairs a stable sort by the first puts in
+    (ts, arrival) order. `err`: one int64 device word the kernels set on a guarded index."""
+    dev = ts.device
+    _reorder_ts(ts, n_arena)
+    _reorder_flag(err, dev)
+    k = len(begins)
+    if len(counts) != k or not 1 <= k <= REORDER_MAX_CHUNKS:
+        raise ValueError(f"reorder_collect: 1 to {REORDER_MAX_CHUNKS} chunks, one count per begin")
+    if any(b < 0 or c < 0 or b + c > n_arena for b, c in zip(begins, counts)):
+        raise ValueError("reorder_collect: a chunk outside the arena")
+    dest = [0]
+    for c in counts:
+        dest.append(dest[-1] + c)
+    total = dest[-1]
+    if total >= 1 << 31:
+        raise ValueError("reorder_collect: at most 2**31 - 1 rows")
+    out = torch.empty((2, total), dtype=torch.int64, device=dev)
+    if total == 0:
+        return out[0], out[1]
+    tab = torch.tensor([list(begins) + [0], dest], dtype=torch.int64).to(dev)
+    m = load()
+    if _is_gpu(ts):
+        m.gpu_reorder_collect(_p(ts), n_arena, _p(tab[0]), _p(tab[1]), k, total, lo, _p(out[0]),
+                              _p(out[1]), _p(err), _stream(ts))
+    else:
+        m.cpu_reorder_collect(_p(ts), n_arena, _p(tab[0]), _p(tab[1]), k, total, lo, _p(out[0]),
+                              _p(out[1]))
+    return out[0], out[1]
+
+
+def reorder_gather(perm: torch.Tensor, src, n_src: int, dst, err: torch.Tensor) -> None:
+    """``dst[c][i] = src[c][perm[i]]`` for the three columns (key id, ts, value bits). `src`
+    columns hold at least `n_src` words, `dst` columns exactly ``perm.numel()``; every index must
+    lie in [0, n_src) (an index outside writes nothing and sets `err` on the device, raises on the
+    CPU)."""
+    dev = perm.device
+    n = _lookup_cols((perm,), ("perm",), dev)
+    _reorder_flag(err, dev)
+    if len(src) != 3 or len(dst) != 3 or n_src < 0:
+        raise ValueError("reorder_gather: three source and three destination columns")
+    for c in src:
+        _check(c, torch.int64, n_src, "src", dev)
+    _lookup_cols(tuple(dst) + (perm,), ("dst", "dst", "dst", "perm"), dev)
+    if n == 0:
+        return
+    m = load()
+    if _is_gpu(perm):
+        m.gpu_reorder_gather(_p(perm), n, *(_p(c) for c in src), n_src, *(_p(c) for c in dst),
+                             _p(err), _stream(perm))
+    else:
+        m.cpu_reorder_gather(_p(perm), n, *(_p(c) for c in src), n_src, *(_p(c) for c in dst))

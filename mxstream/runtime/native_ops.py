@@ -2266,13 +2266,17 @@ class _NativeTwoSidedOp(Operator):
                     # the flush switched to the host operator: it takes the rest of the pass
                     return out + self.fallback.process(expand_columns(items[i:]))
                 self.wm = it.ts
-                if self.op is not None:
+                if self._has_state():
                     out.extend(self._on_watermark(it.ts))
                 out.append(it)
             else:
                 self.pending.append(it)
         out.extend(self._flush())
         return out
+
+    def _has_state(self) -> bool:
+        """Native state exists: a watermark acts on it, and unsupported data is an error."""
+        return self.op is not None
 
     def on_processing_time(self, now):
         if self.fallback is not None:
@@ -2591,17 +2595,26 @@ class NativeSustainOp(_NativeTwoSidedOp):
     no int or float, values of both kinds, a double key, mixed key types, a negative integer key
     or one at or above `dense_limit`, a record without a timestamp and a timestamp at or beyond
     2**62 are unsupported data: the host operator before native state exists, an error
-    afterwards."""
+    afterwards.
+
+    `ordered` (``EventTimeOrdered(rule)``): a flush pushes the batch into an EventOrderBuffer
+    (runtime/reorder_operator.py) and emits nothing; a watermark releases the rows it has
+    reached, in (timestamp, arrival) order, and feeds them to the engine, whose rows leave before
+    the watermark is forwarded. A row at or behind the watermark on arrival is dropped and
+    counted in ``num_late_records_dropped``. The buffer may exist before the engine does; either
+    is native state."""
 
     name = "KeyedProcess(native sustained)"
     # what NativeBurstOp, the same plumbing around another engine, names differently
     fn_name, snap_key, snap_what = "SustainedAlert", "sustained", "sustained-alert"
 
     def __init__(self, *, fn, key_pos: int, device: str, fallback_factory,
-                 dense_limit: int = 1 << 26):
+                 dense_limit: int = 1 << 26, ordered: bool = False):
         super().__init__(key_pos=(key_pos,), val_pos=(fn.field,), layout=("k",), ok_arities=(),
                          device=device, fallback_factory=fallback_factory)
         self.fn_spec = tuple(fn.native)
+        self.ordered = bool(ordered)
+        self.buf = None   # the EventOrderBuffer of an ordered operator, from its first batch on
         self.when, self.threshold = fn.when, fn.threshold
         self._rule(fn)
         self.key_pos, self.val_pos = key_pos, fn.field
@@ -2703,7 +2716,7 @@ class NativeSustainOp(_NativeTwoSidedOp):
         except TypeError as e:
             # Unsupported data for the native path: the exact host operator, while no native
             # state exists yet.
-            if self.op is not None:
+            if self._has_state():
                 if isinstance(e, _NoTimestamp):
                     raise ValueError(f"{self.fn_name}: a record without an event "
                                      "timestamp") from None
@@ -2711,32 +2724,74 @@ class NativeSustainOp(_NativeTwoSidedOp):
             self._to_fallback()
             return self.fallback.process(expand_columns(items))
         self.is_float = kinds
+        if self.ordered:
+            if self.buf is None:
+                self._build_buffer()
+            self.buf.push(keys, ts, bits, bounds=(tmin, tmax))
+            self._late = self.buf.metrics.num_late_records_dropped
+            return []
+        return self._rule_rows(keys, bits, ts)
+
+    def _rule_rows(self, keys, bits, ts) -> list:
+        """The engine over a batch in the order given; its rows as host ColumnBatches."""
         if self.op is None:
             self._build()
         out = []
-        for cols in self.op.process(keys, bits, ts, is_float=kinds[0]):
+        is_float = self.is_float[0]
+        for cols in self.op.process(keys, bits, ts, is_float=is_float):
             key, code, since, val, t = (c.cpu().numpy() for c in cols)
-            vals = np.ascontiguousarray(val).view(np.float64) if kinds[0] else val
+            vals = np.ascontiguousarray(val).view(np.float64) if is_float else val
             out.append(ColumnBatch(int(key.size), [key, code, since, vals],
                                    (FK_STR if self.str_keys else FK_LONG, FK_LONG, FK_LONG,
-                                    FK_DOUBLE if kinds[0] else FK_LONG),
+                                    FK_DOUBLE if is_float else FK_LONG),
                                    self.dict if self.str_keys else None, t,
                                    self._subtasks(key), False))
         return out
 
+    def _has_state(self) -> bool:
+        return self.op is not None or self.buf is not None
+
+    def _build_buffer(self) -> None:
+        from .reorder_operator import EventOrderBuffer
+
+        self.buf = EventOrderBuffer(torch.device(self.device))
+        self.buf.wm = self.wm   # rows are late against it from the start
+
     def _on_watermark(self, wm: int) -> list:
-        return self.op.advance_watermark(wm)
+        out = []
+        if self.buf is not None:
+            cols = self.buf.release(wm)
+            if cols is not None:
+                # (the columns may be slices of the buffer: the engine reads them before the
+                # buffer is touched again)
+                keys, ts, bits = cols
+                out = self._rule_rows(keys, bits, ts)
+        if self.op is not None:
+            out.extend(self.op.advance_watermark(wm))
+        return out
 
     def snapshot(self) -> dict:
         snap = super().snapshot()
         snap[self.snap_key] = self.fn_spec
+        if self.ordered:
+            snap["ordered"] = True
+            if self.buf is not None:
+                es = self.buf.snapshot_state()
+                snap["reorder"] = {"columns": es.columns, "meta": es.meta}
         return snap
 
     def restore(self, snap: dict) -> None:
         spec = snap.get(self.snap_key)
         if "fallback" not in snap and (spec is None or not _same_spec(spec, self.fn_spec)):
             raise ValueError(f"checkpoint of a different {self.snap_what} function")
+        if "fallback" not in snap and bool(snap.get("ordered", False)) != self.ordered:
+            raise ValueError(f"checkpoint of a {self.snap_what} function "
+                             f"{'with' if snap.get('ordered') else 'without'} event-time order")
         super().restore(snap)
+        ro = snap.get("reorder")
+        if ro is not None and "fallback" not in snap:
+            self._build_buffer()
+            self.buf.restore_state(ro["columns"], ro["meta"])
 
 
 class NativeBurstOp(NativeSustainOp):

@@ -436,7 +436,8 @@ class KeyedProcessOp(KeyedOperator):
         c.time_domain = domain
         self.fn.on_timer(ts, c, col)
         sub = self.subtask_of(key)
-        return [Rec(v, ts, sub) for v in col.items]
+        # an item collected with a stamp of its own (Collector.collect_at) keeps it
+        return [Rec(v, col.stamps.get(i, ts), sub) for i, v in enumerate(col.items)]
 
     def on_watermark(self, wm):
         self.wm = wm
