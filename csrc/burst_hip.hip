@@ -2,9 +2,11 @@
 // the key's breach history followed by a segmented wave scan (declarations, the model and the
 // summary algebra: csrc/mxs_burst.h; C++ twin: csrc/burst_cpu.cpp).
 //
-// scan: the batch arrives stably sorted by key. Ownership is sustain_scan_kernel's: a wave owns
-// the key runs that BEGIN in its 64 sorted rows and walks on a run that leaves the chunk, so a
-// key's ring and row have one reading and one writing wave and no atomics touch them.
+// scan: the batch arrives stably sorted by key and is scanned in the frame of csrc/rule_scan.h
+// (rule_heads, rule_owned, rule_before, rule_edge_append, rule_run_goes_on): a wave owns the key runs that
+// BEGIN in its 64 sorted rows and walks on a run that leaves the chunk, so a key's ring and row
+// have one reading and one writing wave and no atomics touch them. This file adds, between the
+// frame's pieces:
 //   look-back  A lane's breach ordinal in its run is a popcount of the breach ballot between the
 //              run's head lane and the lane. The chunk's breach timestamps are staged in a
 //              per-wave LDS strip at their wave-wide breach rank; "the times-th most recent
@@ -20,28 +22,21 @@
 //              collects them in the LDS carry (filled from the stored ring at the head chunk,
 //              before any store to that key) and lanes 0..times-1 store the slots the batch
 //              wrote when the run ends. No lane reads from global memory what another lane
-//              stored in this launch. The lane that ends a run stores (since, meta).
-// Transitions are appended with one reservation per wave and chunk that has any, each tagged
-// ``arrival index << 1 | code``; sustain_gather turns the sorted rows into the five columns.
+//              stored in this launch (the frame's pieces load only the sorted keys and the
+//              arrival indices and store only the appended rows, which nothing here loads). The
+//              lane that ends a run stores (since, meta).
+// sustain_gather (csrc/sustain_hip.hip), the family's gather, turns the appended rows sorted by
+// tag into the five columns.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
 #include <string>
 
 #include "mxs_burst.h"
+#include "rule_scan.h"
 
 namespace mxs {
 namespace {
-
-#define BURST_CHECK(x)                                                                      \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
-typedef long long ll2 __attribute__((ext_vector_type(2)));
 
 constexpr int kBurstBlock = 256;
 constexpr int kBurstWaves = kBurstBlock / 64;
@@ -70,7 +65,7 @@ __global__ __launch_bounds__(kBurstBlock) void burst_scan_kernel(
   int64_t* carry = s_carry[threadIdx.x >> 6];
   const unsigned long long le = (2ull << lane) - 1ull;   // lanes <= lane
   const unsigned long long ge = ~((1ull << lane) - 1ull);  // lanes >= lane
-  // `base` is the same for a wave's 64 lanes, and so is every loop condition below.
+  // Every loop condition is wave-uniform (csrc/rule_scan.h).
   for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n;
        base += (int64_t)gridDim.x * blockDim.x) {
     bool cont = false;  // walking on a run that left the wave's own chunk
@@ -79,23 +74,12 @@ __global__ __launch_bounds__(kBurstBlock) void burst_scan_kernel(
     int64_t ck = 0, cs = 0;
     int cf = 0, cpos = 0, cheld = 0, bpos = 0, bn = 0;
     for (int64_t b0 = base;; b0 += 64) {
-      const int64_t i = b0 + lane;
-      const bool in = i < n;
-      const int64_t k = in ? skeys[i] : 0;
-      bool act, head = false;
-      unsigned long long hm = 0;
-      if (!cont) {
-        head = in && (i == 0 || skeys[i - 1] != k);
-        hm = __ballot(head);
-        if (!hm) break;  // the whole chunk continues an earlier run: that run's wave walks it
-        act = in && lane >= __ffsll((long long)hm) - 1;
-      } else {
-        act = in && k == ck;  // sorted: a prefix of the chunk, lane 0 included
-      }
-      const bool tail = act && (i + 1 == n || skeys[i + 1] != k);
-      const int64_t src = act ? perm[i] : 0;
-      // Out-of-range ids never reach memory (the callers check both before the launch).
-      const bool ok = act && (uint64_t)k < (uint64_t)cap && (uint64_t)src < (uint64_t)n;
+      RuleFrame fr = rule_heads(skeys, n, b0, lane, cont);
+      if (fr.leave) break;
+      rule_owned(skeys, perm, n, cap, lane, cont, ck, fr);
+      const int64_t k = fr.k, src = fr.src;
+      const bool head = fr.head, act = fr.act, tail = fr.tail, ok = fr.ok;
+      const unsigned long long hm = fr.hm;
       const int64_t t = ok ? ts[src] : 0;
       const bool br = ok && sustain_breach(kind, when, vals[src], thr);
       const unsigned long long tm = __ballot(tail), bm = __ballot(br);
@@ -144,28 +128,16 @@ __global__ __launch_bounds__(kBurstBlock) void burst_scan_kernel(
           f = g;
         }
       }
-      // The state after this element, and the one before it: the previous lane's, or the carry.
+      // The state after this element, and the one before it.
       int64_t s1 = cs;
       int f1 = cf;
       if (vk == kOff) s1 = 0, f1 = 0;
       else if (vk == kOn || (vk == kSet && !cf)) s1 = vt, f1 = 1;
-      int64_t s0 = __shfl_up(s1, 1);
-      int f0 = __shfl_up(f1, 1);
-      if (head || lane == 0) s0 = cs, f0 = cf;
+      const int64_t s0 = rule_before(s1, cs, head, lane);
+      const int f0 = rule_before(f1, cf, head, lane);
       const bool fire = ok && f1 && !f0;
       const bool resolve = ok && !f1 && f0;
-      const bool emit = fire || resolve;
-      const unsigned long long m = __ballot(emit);
-      uint32_t wb = 0;
-      if (lane == 0 && m) wb = atomicAdd(out_n, (uint32_t)__popcll(m));
-      wb = __shfl(wb, 0);
-      if (emit) {
-        const int64_t q = (int64_t)wb + __popcll(m & ((1ull << lane) - 1ull));
-        if (q < n) {  // at most one row per element: always true
-          out_tag[q] = (src << 1) | (fire ? 1 : 0);
-          out_since[q] = fire ? s1 : s0;
-        }
-      }
+      rule_edge_append(fire, resolve, src, s1, s0, n, out_tag, out_since, out_n, lane);
       // Ring stores: the breaches among the run's last `times` in this chunk.
       const bool ends = act && (tm & ge);  // the lane's run ends in this chunk
       const int tl = ends ? __ffsll((long long)(tm & ge)) - 1 : 63;
@@ -178,9 +150,7 @@ __global__ __launch_bounds__(kBurstBlock) void burst_scan_kernel(
         r.x = f1 ? s1 : 0, r.y = burst_meta(f1, held1, pa);
         row[k] = r;  // one 16-byte store by the lane that ends the run
       }
-      // The run of lane 63 goes on in the next chunk: walk it.
-      const unsigned long long am = __ballot(act);
-      const bool goes = ((am >> 63) & 1ull) && !((tm >> 63) & 1ull);
+      const bool goes = rule_run_goes_on(act, tm);
       if (!cont && !goes) break;
       if (!cont) {  // the head chunk of a walk: the key's stored ring, before any store to it
         const int64_t k63 = __shfl(k, 63);
@@ -211,12 +181,6 @@ __global__ __launch_bounds__(kBurstBlock) void burst_scan_kernel(
   }
 }
 
-int grid_of(int64_t n) {
-  int64_t g = (n + kBurstBlock - 1) / kBurstBlock;
-  if (g < 1) g = 1;
-  return (int)(g < kBurstMaxGrid ? g : kBurstMaxGrid);
-}
-
 }  // namespace
 
 namespace gpu {
@@ -239,12 +203,13 @@ void burst_scan(const int64_t* skeys, const int64_t* perm, const int64_t* vals, 
     throw std::invalid_argument("burst_scan: unknown value kind");
   if (out_n == nullptr) throw std::invalid_argument("burst_scan: no row counter");
   hipStream_t s = (hipStream_t)stream;
-  BURST_CHECK(hipMemsetAsync(out_n, 0, sizeof(uint32_t), s));
+  MXS_HIP_CHECK(hipMemsetAsync(out_n, 0, sizeof(uint32_t), s));
   if (n == 0) return;
-  hipLaunchKernelGGL(burst_scan_kernel, dim3(grid_of(n)), dim3(kBurstBlock), 0, s, skeys, perm,
-                     vals, ts, n, kind, when, lookup_f64(thr_bits), times, within, ring,
-                     reinterpret_cast<ll2*>(row), cap, out_tag, out_since, out_n);
-  BURST_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(burst_scan_kernel, dim3(grid_of(n, kBurstBlock, kBurstMaxGrid)),
+                     dim3(kBurstBlock), 0, s, skeys, perm, vals, ts, n, kind, when,
+                     lookup_f64(thr_bits), times, within, ring, reinterpret_cast<ll2*>(row), cap,
+                     out_tag, out_since, out_n);
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

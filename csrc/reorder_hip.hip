@@ -13,25 +13,12 @@
 #include <string>
 
 #include "mxs_reorder.h"
+#include "rule_scan.h"
 
 namespace mxs {
 namespace {
 
-#define REORDER_CHECK(x)                                                                    \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
 constexpr int kReorderBlock = 256;
-
-int grid_of(int64_t n, int per_block, int cap) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < cap ? g : cap);
-}
 
 // ---- cut -----------------------------------------------------------------------------------
 // One lane per chunk. A chunk whose bounds do not lie in the arena is cut at its begin.
@@ -113,7 +100,7 @@ void reorder_cut(const int64_t* ts, int64_t n_arena, const int64_t* begin, const
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(reorder_cut_kernel, dim3(grid_of(k, kReorderBlock, 1 << 16)),
                      dim3(kReorderBlock), 0, s, ts, n_arena, begin, end, k, w, cut);
-  REORDER_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void reorder_collect(const int64_t* ts, int64_t n_arena, const int64_t* begin, const int64_t* dest,
@@ -126,7 +113,7 @@ void reorder_collect(const int64_t* ts, int64_t n_arena, const int64_t* begin, c
   hipLaunchKernelGGL(reorder_collect_kernel, dim3(grid_of(ntiles, 1, 1 << 16)),
                      dim3(kReorderBlock), 0, s, ts, n_arena, begin, dest, (int32_t)k, total, lo,
                      ntiles, out_key, out_src, err);
-  REORDER_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void reorder_gather(const int64_t* perm, int64_t m, const int64_t* src_key, const int64_t* src_ts,
@@ -137,7 +124,7 @@ void reorder_gather(const int64_t* perm, int64_t m, const int64_t* src_key, cons
   hipLaunchKernelGGL(reorder_gather_kernel, dim3(grid_of(m, kReorderBlock, 1 << 16)),
                      dim3(kReorderBlock), 0, s, perm, m, src_key, src_ts, src_bits, n_src, dst_key,
                      dst_ts, dst_bits, err);
-  REORDER_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

@@ -2,35 +2,23 @@
 // run as a segmented wave scan (declarations, the model and the summary algebra:
 // csrc/mxs_sustain.h; C++ twin: csrc/sustain_cpu.cpp).
 //
-// scan: the batch arrives stably sorted by key. A wave owns the key runs that BEGIN in its 64
-// sorted rows: their elements in this chunk are one segmented inclusive scan (a run head starts
-// a segment; every lane loads its key's 16-byte row as the carry), so short runs share a wave.
-// A run that leaves the chunk is walked on by the same wave, 64 elements at a time, with the
-// carry in registers; the rows before a chunk's first head belong to such a walk and are
-// skipped by the chunk's own wave. A key's row therefore has one reader and one writer: the
-// lane that ends the run stores it, no atomics on the state. Transitions are appended with one
-// reservation per wave and chunk that has any (ballot / popcount), each tagged
-// ``arrival index << 1 | code``.
-// gather: the appended rows, sorted by tag, become the five output columns.
+// scan: the batch arrives stably sorted by key and is scanned in the frame of csrc/rule_scan.h:
+// a wave owns the key runs that begin in its 64 sorted rows and walks on a run that leaves them,
+// so a key's 16-byte row has one reader and one writer and no atomics touch the state; the
+// transitions are appended with one reservation per wave and chunk. What is this rule's own is
+// the summary and its segmented scan, and the edges it takes from the states.
+// gather: the appended rows, sorted by tag, become the five output columns. It is the gather of
+// every rule in that frame (burst_update launches it too).
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
 #include <string>
 
 #include "mxs_sustain.h"
+#include "rule_scan.h"
 
 namespace mxs {
 namespace {
-
-#define SUSTAIN_CHECK(x)                                                                    \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
-typedef long long ll2 __attribute__((ext_vector_type(2)));
 
 constexpr int kSustainBlock = 256;
 constexpr int kSustainMaxGrid = 8192;
@@ -69,28 +57,17 @@ __global__ __launch_bounds__(kSustainBlock) void sustain_scan_kernel(
     int when, double thr, int64_t for_ms, ll2* __restrict__ state, int64_t cap,
     int64_t* __restrict__ out_tag, int64_t* __restrict__ out_since, uint32_t* __restrict__ out_n) {
   const int lane = threadIdx.x & 63;
-  // `base` is the same for a wave's 64 lanes, and so is every loop condition below.
+  // Every loop condition is wave-uniform (csrc/rule_scan.h).
   for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < n;
        base += (int64_t)gridDim.x * blockDim.x) {
     bool cont = false;  // walking on a run that left the wave's own chunk
     int64_t ck = 0, cs = kSustainNone, cf = 0;
     for (int64_t b0 = base;; b0 += 64) {
-      const int64_t i = b0 + lane;
-      const bool in = i < n;
-      const int64_t k = in ? skeys[i] : 0;
-      bool act, head = false;
-      if (!cont) {
-        head = in && (i == 0 || skeys[i - 1] != k);
-        const unsigned long long hm = __ballot(head);
-        if (!hm) break;  // the whole chunk continues an earlier run: that run's wave walks it
-        act = in && lane >= __ffsll((long long)hm) - 1;
-      } else {
-        act = in && k == ck;  // sorted: a prefix of the chunk, lane 0 included
-      }
-      const bool tail = act && (i + 1 == n || skeys[i + 1] != k);
-      const int64_t src = act ? perm[i] : 0;
-      // Out-of-range ids never reach memory (the callers check both before the launch).
-      const bool ok = act && (uint64_t)k < (uint64_t)cap && (uint64_t)src < (uint64_t)n;
+      RuleFrame fr = rule_heads(skeys, n, b0, lane, cont);
+      if (fr.leave) break;
+      rule_owned(skeys, perm, n, cap, lane, cont, ck, fr);
+      const int64_t k = fr.k, src = fr.src;
+      const bool ok = fr.ok;
       const int64_t t = ok ? ts[src] : 0;
       const bool br = ok && sustain_breach(kind, when, vals[src], thr);
       if (!cont) {
@@ -101,7 +78,7 @@ __global__ __launch_bounds__(kSustainBlock) void sustain_scan_kernel(
       }
       // Inclusive segmented wave scan (Hillis-Steele) of the summaries; y is the earlier one.
       Summary v = br ? Summary{t, t, 0} : Summary{kSustainNone, 0, 1};
-      int f = head;
+      int f = fr.head;
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {
         Summary y;
@@ -114,36 +91,23 @@ __global__ __launch_bounds__(kSustainBlock) void sustain_scan_kernel(
           f = g;
         }
       }
-      // The state after this element, and the one before it: the previous lane's, or the carry.
+      // The state after this element, and the one before it.
       int64_t s1 = v.a, f1 = v.b;
       if (!v.r) {
         s1 = cs, f1 = cf;
         sustain_apply(v.a, v.b, for_ms, s1, f1);
       }
-      int64_t s0 = __shfl_up(s1, 1), f0 = __shfl_up(f1, 1);
-      if (head || lane == 0) s0 = cs, f0 = cf;
+      const int64_t s0 = rule_before(s1, cs, fr.head, lane);
+      const int64_t f0 = rule_before(f1, cf, fr.head, lane);
       const bool fire = ok && f1 && !f0;
       const bool resolve = ok && !br && f0;
-      const bool emit = fire || resolve;
-      const unsigned long long m = __ballot(emit);
-      uint32_t wb = 0;
-      if (lane == 0 && m) wb = atomicAdd(out_n, (uint32_t)__popcll(m));
-      wb = __shfl(wb, 0);
-      if (emit) {
-        const int64_t q = (int64_t)wb + __popcll(m & ((1ull << lane) - 1ull));
-        if (q < n) {  // at most one row per element: always true
-          out_tag[q] = (src << 1) | (fire ? 1 : 0);
-          out_since[q] = fire ? s1 : s0;
-        }
-      }
-      if (tail && ok) {
+      rule_edge_append(fire, resolve, src, s1, s0, n, out_tag, out_since, out_n, lane);
+      if (fr.tail && ok) {
         ll2 row;
         row.x = s1, row.y = f1;
         state[k] = row;  // one 16-byte store by the lane that ends the run
       }
-      // The run of lane 63 goes on in the next chunk: walk it.
-      const unsigned long long am = __ballot(act), tm = __ballot(tail);
-      if (!((am >> 63) & 1ull) || ((tm >> 63) & 1ull)) break;
+      if (!rule_run_goes_on(fr.act, __ballot(fr.tail))) break;
       cont = true;
       ck = __shfl(k, 63);
       cs = __shfl(s1, 63);
@@ -171,12 +135,6 @@ __global__ __launch_bounds__(kSustainBlock) void sustain_gather_kernel(
   }
 }
 
-int grid_of(int64_t n) {
-  int64_t g = (n + kSustainBlock - 1) / kSustainBlock;
-  if (g < 1) g = 1;
-  return (int)(g < kSustainMaxGrid ? g : kSustainMaxGrid);
-}
-
 }  // namespace
 
 namespace gpu {
@@ -195,12 +153,13 @@ void sustain_scan(const int64_t* skeys, const int64_t* perm, const int64_t* vals
     throw std::invalid_argument("sustain_scan: unknown value kind");
   if (out_n == nullptr) throw std::invalid_argument("sustain_scan: no row counter");
   hipStream_t s = (hipStream_t)stream;
-  SUSTAIN_CHECK(hipMemsetAsync(out_n, 0, sizeof(uint32_t), s));
+  MXS_HIP_CHECK(hipMemsetAsync(out_n, 0, sizeof(uint32_t), s));
   if (n == 0) return;
-  hipLaunchKernelGGL(sustain_scan_kernel, dim3(grid_of(n)), dim3(kSustainBlock), 0, s, skeys,
-                     perm, vals, ts, n, kind, when, lookup_f64(thr_bits), for_ms,
-                     reinterpret_cast<ll2*>(state), cap, out_tag, out_since, out_n);
-  SUSTAIN_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(sustain_scan_kernel, dim3(grid_of(n, kSustainBlock, kSustainMaxGrid)),
+                     dim3(kSustainBlock), 0, s, skeys, perm, vals, ts, n, kind, when,
+                     lookup_f64(thr_bits), for_ms, reinterpret_cast<ll2*>(state), cap, out_tag,
+                     out_since, out_n);
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void sustain_gather(const int64_t* tags, const int64_t* since, int64_t m, const int64_t* keys,
@@ -209,10 +168,10 @@ void sustain_gather(const int64_t* tags, const int64_t* since, int64_t m, const 
                     intptr_t stream) {
   if (m < 0 || m > n) throw std::invalid_argument("sustain_gather: bad row count");
   if (m == 0) return;
-  hipLaunchKernelGGL(sustain_gather_kernel, dim3(grid_of(m)), dim3(kSustainBlock), 0,
-                     (hipStream_t)stream, tags, since, m, keys, vals, ts, n, out_key, out_code,
-                     out_since, out_val, out_ts);
-  SUSTAIN_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(sustain_gather_kernel, dim3(grid_of(m, kSustainBlock, kSustainMaxGrid)),
+                     dim3(kSustainBlock), 0, (hipStream_t)stream, tags, since, m, keys, vals, ts,
+                     n, out_key, out_code, out_since, out_val, out_ts);
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

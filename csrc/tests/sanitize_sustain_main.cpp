@@ -6,57 +6,17 @@
 // equal timestamps and empty batches, against a model written as a map of optional states; and
 // checks that every refused batch leaves the table untouched.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <map>
-#include <stdexcept>
-#include <tuple>
 #include <utility>
 #include <vector>
 
 #include "mxs_sustain.h"
+#include "sanitize_util.h"
 
 using namespace mxs;
 
 namespace {
-
-#define REQUIRE(c)                                                  \
-  do {                                                              \
-    if (!(c)) {                                                     \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); \
-      std::exit(1);                                                 \
-    }                                                               \
-  } while (0)
-
-typedef std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> Row;  // key, code, since, bits, ts
-
-struct Rng {
-  uint64_t s;
-  uint64_t next() {
-    s = s * 6364136223846793005ull + 1442695040888963407ull;
-    return s >> 33;
-  }
-  int64_t below(int64_t n) { return (int64_t)(next() % (uint64_t)n); }
-};
-
-int64_t bits_of(double d) {
-  int64_t b;
-  std::memcpy(&b, &d, sizeof b);
-  return b;
-}
-
-bool compare(int when, double a, double b) {
-  switch (when) {
-    case kLookupGt: return a > b;
-    case kLookupGe: return a >= b;
-    case kLookupLt: return a < b;
-    case kLookupLe: return a <= b;
-    case kLookupEq: return a == b;
-    default: return a != b;
-  }
-}
 
 // SustainedAlert record by record; a key without an entry has no open run.
 struct Model {
@@ -174,17 +134,6 @@ void edges() {
   got = run(m, {2, 2}, {b, b}, {-kSustainTsLimit + 1, kSustainTsLimit - 1}, state);
   REQUIRE(got == (std::vector<Row>{Row(2, 1, -kSustainTsLimit + 1, b, kSustainTsLimit - 1)}));
   REQUIRE(run(m, {}, {}, {}, state).empty());
-}
-
-template <class F>
-void refused(F f) {
-  bool threw = false;
-  try {
-    f();
-  } catch (const std::invalid_argument&) {
-    threw = true;
-  }
-  REQUIRE(threw);
 }
 
 void refusals() {

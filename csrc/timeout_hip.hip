@@ -17,19 +17,10 @@
 #include <string>
 
 #include "mxs_timeout.h"
+#include "rule_scan.h"
 
 namespace mxs {
 namespace {
-
-#define TIMEOUT_CHECK(x)                                                                    \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
-typedef long long ll2 __attribute__((ext_vector_type(2)));
 
 constexpr int kTimeoutBlock = 256;
 constexpr int kTimeoutWaves = kTimeoutBlock / 64;
@@ -38,12 +29,6 @@ constexpr int kEmitRounds = kTimeoutTile / kTimeoutBlock;        // key ids per 
 constexpr int kTimeoutMaxGrid = 1 << 20;  // larger tables stride over their tiles
 constexpr int kTimeoutTileLog2 = 12;
 static_assert((1 << kTimeoutTileLog2) == kTimeoutTile, "tile size");
-
-int grid_of(int64_t n, int per_block, int cap) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < cap ? g : cap);
-}
 
 __device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
 
@@ -259,7 +244,7 @@ void timeout_update(const int64_t* skeys, const int64_t* perm, const int64_t* ts
   hipLaunchKernelGGL(timeout_update_kernel, dim3(grid_of(n, kTimeoutBlock, 8192)),
                      dim3(kTimeoutBlock), 0, (hipStream_t)stream, skeys, perm, ts, n, timeout,
                      reinterpret_cast<ll2*>(state), deadline, tile_min, cap);
-  TIMEOUT_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void timeout_mask(const int64_t* deadline, int64_t cap, int64_t w, int64_t* tile_min,
@@ -275,7 +260,7 @@ void timeout_mask(const int64_t* deadline, int64_t cap, int64_t w, int64_t* tile
   else
     hipLaunchKernelGGL(timeout_mask_kernel<false>, grid, dim3(kTimeoutBlock), 0, s, deadline, cap,
                        w, ntiles, tile_min, words, counts);
-  TIMEOUT_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 // `words`, `counts` and `offsets` must be timeout_mask's and lookup_scan's output for these same
@@ -293,7 +278,7 @@ void timeout_emit(const int64_t* state, int64_t* deadline, int64_t cap, const ui
                      dim3(kTimeoutBlock), 0, (hipStream_t)stream,
                      reinterpret_cast<const ll2*>(state), deadline, cap, ntiles, words, counts,
                      offsets, total, out_key, out_count, out_last, out_deadline);
-  TIMEOUT_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

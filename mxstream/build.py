@@ -152,7 +152,8 @@ def _build_sanitize_program(name: str, sources: list[str], verbose: bool) -> Pat
     srcs = [CSRC / s for s in sources]
     cmd = ["g++", "-std=c++17", *SANITIZE_FLAGS, f"-I{CSRC}", "-I/opt/rocm/include",
            "-D__HIP_PLATFORM_AMD__", *[str(s) for s in srcs], "-o", str(exe)]
-    newest = max(s.stat().st_mtime for s in srcs + sorted(CSRC.glob("*.h")))
+    hdrs = sorted(CSRC.glob("*.h")) + sorted((CSRC / "tests").glob("*.h"))
+    newest = max(s.stat().st_mtime for s in srcs + hdrs)
     if not exe.exists() or exe.stat().st_mtime < newest:
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:

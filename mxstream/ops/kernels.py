@@ -1230,6 +1230,51 @@ def sustain_table(cap: int, device) -> torch.Tensor:
     return state
 
 
+def _rule_update(row: torch.Tensor, keys, vals, ts, bounds, name: str, twin, scan):
+    """What the rules over a batch sorted by key share once their parameters are checked (`row`
+    is the rule's [cap, 2] table, `name` the caller's for messages): the bounds, then on the CPU
+    ``twin(*five output pointers)`` -> rows, else the sort by key, ``scan(skeys, perm, tags,
+    since, count, stream)`` (pointers), the count's readback, the sort by arrival index and the
+    family's gather. Five columns in arrival order."""
+    dev = row.device
+    cap, n = row.shape[0], keys.numel()
+    out = torch.empty((5, n), dtype=torch.int64, device=dev)
+    if n == 0:
+        return tuple(out[c] for c in range(5))
+    if bounds is None or not _is_gpu(row):
+        lo, hi, tmin, tmax = torch.stack([keys.min(), keys.max(), ts.min(), ts.max()]).tolist()
+    else:
+        lo, (hi, tmin, tmax) = 0, (int(b) for b in bounds)
+    if lo < 0 or hi >= cap:
+        raise ValueError(f"{name}: keys must lie in [0, {cap})")
+    if tmin <= -SUSTAIN_TS_LIMIT or tmax >= SUSTAIN_TS_LIMIT:
+        raise TypeError(f"{name}: a timestamp at or beyond 2**62")
+    if not _is_gpu(row):
+        rows = twin(*(_p(out[c]) for c in range(5)))
+        return tuple(out[c, :rows] for c in range(5))
+    st = _stream(row)
+    if n == 1:
+        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
+    scratch = torch.empty((2, n), dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    scan(_p(skeys), _p(perm), _p(scratch[0]), _p(scratch[1]), _p(count), st)
+    rows = int(count.item())  # the only readback
+    if not 0 <= rows <= n:
+        raise RuntimeError(f"{name}: more transitions than rows")
+    if rows == 0:
+        return tuple(out[c, :0] for c in range(5))
+    # Arrival order: the tags are ``arrival << 1 | code``, one per element at most.
+    tags, since = scratch[0, :rows], scratch[1, :rows]
+    if rows > 1:
+        tags, since = sort_pairs(tags, since, bits=(n - 1).bit_length() + 1)
+    load().gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
+                              *(_p(out[c]) for c in range(5)), st)
+    return tuple(out[c, :rows] for c in range(5))
+
+
 def sustain_update(state: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, ts: torch.Tensor,
                    *, kind: int, when, threshold_bits: int, for_ms: int,
                    bounds: tuple | None = None):
@@ -1256,44 +1301,12 @@ def sustain_update(state: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, 
         raise ValueError("sustain_update: threshold_bits must be an int64 bit pattern")
     if n >= 1 << 31:
         raise ValueError("sustain_update: at most 2**31 - 1 rows per batch")
-    out = torch.empty((5, n), dtype=torch.int64, device=dev)
-    if n == 0:
-        return tuple(out[c] for c in range(5))
-    if bounds is None or not _is_gpu(state):
-        lo, hi, tmin, tmax = torch.stack([keys.min(), keys.max(), ts.min(), ts.max()]).tolist()
-    else:
-        lo, (hi, tmin, tmax) = 0, (int(b) for b in bounds)
-    if lo < 0 or hi >= cap:
-        raise ValueError(f"sustain_update: keys must lie in [0, {cap})")
-    if tmin <= -SUSTAIN_TS_LIMIT or tmax >= SUSTAIN_TS_LIMIT:
-        raise TypeError("sustain_update: a timestamp at or beyond 2**62")
-    m = load()
-    if not _is_gpu(state):
-        rows = m.cpu_sustain_update(_p(keys), _p(vals), _p(ts), n, kind, code, tbits, for_ms,
-                                    _p(state), cap, *(_p(out[c]) for c in range(5)))
-        return tuple(out[c, :rows] for c in range(5))
-    st = _stream(state)
-    if n == 1:
-        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
-    else:
-        idx = torch.arange(n, dtype=torch.int64, device=dev)
-        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
-    scratch = torch.empty((2, n), dtype=torch.int64, device=dev)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
-    m.gpu_sustain_scan(_p(skeys), _p(perm), _p(vals), _p(ts), n, kind, code, tbits, for_ms,
-                       _p(state), cap, _p(scratch[0]), _p(scratch[1]), _p(count), st)
-    rows = int(count.item())  # the only readback
-    if not 0 <= rows <= n:
-        raise RuntimeError("sustain_update: more transitions than rows")
-    if rows == 0:
-        return tuple(out[c, :0] for c in range(5))
-    # Arrival order: the tags are ``arrival << 1 | code``, one per element at most.
-    tags, since = scratch[0, :rows], scratch[1, :rows]
-    if rows > 1:
-        tags, since = sort_pairs(tags, since, bits=(n - 1).bit_length() + 1)
-    m.gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
-                         *(_p(out[c]) for c in range(5)), st)
-    return tuple(out[c, :rows] for c in range(5))
+    rule = (n, kind, code, tbits, for_ms, _p(state), cap)
+    return _rule_update(
+        state, keys, vals, ts, bounds, "sustain_update",
+        lambda *outs: load().cpu_sustain_update(_p(keys), _p(vals), _p(ts), *rule, *outs),
+        lambda skeys, perm, *outs: load().gpu_sustain_scan(skeys, perm, _p(vals), _p(ts), *rule,
+                                                           *outs))
 
 
 # ---- burst alerts (csrc/mxs_burst.h) ------------------------------------------------------------
@@ -1346,44 +1359,12 @@ def burst_update(ring: torch.Tensor, row: torch.Tensor, keys: torch.Tensor, vals
         raise ValueError("burst_update: threshold_bits must be an int64 bit pattern")
     if n >= 1 << 31:
         raise ValueError("burst_update: at most 2**31 - 1 rows per batch")
-    out = torch.empty((5, n), dtype=torch.int64, device=dev)
-    if n == 0:
-        return tuple(out[c] for c in range(5))
-    if bounds is None or not _is_gpu(row):
-        lo, hi, tmin, tmax = torch.stack([keys.min(), keys.max(), ts.min(), ts.max()]).tolist()
-    else:
-        lo, (hi, tmin, tmax) = 0, (int(b) for b in bounds)
-    if lo < 0 or hi >= cap:
-        raise ValueError(f"burst_update: keys must lie in [0, {cap})")
-    if tmin <= -SUSTAIN_TS_LIMIT or tmax >= SUSTAIN_TS_LIMIT:
-        raise TypeError("burst_update: a timestamp at or beyond 2**62")
-    m = load()
-    if not _is_gpu(row):
-        rows = m.cpu_burst_update(_p(keys), _p(vals), _p(ts), n, kind, code, tbits, times, within,
-                                  _p(ring), _p(row), cap, *(_p(out[c]) for c in range(5)))
-        return tuple(out[c, :rows] for c in range(5))
-    st = _stream(row)
-    if n == 1:
-        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
-    else:
-        idx = torch.arange(n, dtype=torch.int64, device=dev)
-        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
-    scratch = torch.empty((2, n), dtype=torch.int64, device=dev)
-    count = torch.empty(1, dtype=torch.int32, device=dev)
-    m.gpu_burst_scan(_p(skeys), _p(perm), _p(vals), _p(ts), n, kind, code, tbits, times, within,
-                     _p(ring), _p(row), cap, _p(scratch[0]), _p(scratch[1]), _p(count), st)
-    rows = int(count.item())  # the only readback
-    if not 0 <= rows <= n:
-        raise RuntimeError("burst_update: more transitions than rows")
-    if rows == 0:
-        return tuple(out[c, :0] for c in range(5))
-    # Arrival order: the tags are ``arrival << 1 | code``, one per element at most.
-    tags, since = scratch[0, :rows], scratch[1, :rows]
-    if rows > 1:
-        tags, since = sort_pairs(tags, since, bits=(n - 1).bit_length() + 1)
-    m.gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
-                         *(_p(out[c]) for c in range(5)), st)
-    return tuple(out[c, :rows] for c in range(5))
+    rule = (n, kind, code, tbits, times, within, _p(ring), _p(row), cap)
+    return _rule_update(
+        row, keys, vals, ts, bounds, "burst_update",
+        lambda *outs: load().cpu_burst_update(_p(keys), _p(vals), _p(ts), *rule, *outs),
+        lambda skeys, perm, *outs: load().gpu_burst_scan(skeys, perm, _p(vals), _p(ts), *rule,
+                                                         *outs))
 
 
 # ---- event-time reorder buffer (csrc/mxs_reorder.h) ---------------------------------------------

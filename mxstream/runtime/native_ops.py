@@ -2463,7 +2463,63 @@ class _NoTimestamp(TypeError):
     """A record without an event timestamp (unsupported data; the host function's ValueError)."""
 
 
-class NativeTimeoutOp(_NativeTwoSidedOp):
+class _NativeKeyedRuleOp(_NativeTwoSidedOp):
+    """The flush of the keyed rules with one input (NativeTimeoutOp, NativeSustainOp): records,
+    host and device column batches become one batch of device columns in arrival order, key ids
+    and timestamps first. A subclass names its function (`fn_name`), gives the columns of a run
+    of records and of a column batch (``_rec_columns``, ``_cb_columns``; `kinds`: the value
+    kinds seen so far, _NativeTwoSidedOp._kind), checks the batch's timestamp range
+    (``_check_ts``) and takes the accepted columns (``_accept``)."""
+
+    fn_name = ""
+
+    def _flush(self) -> list:
+        items, self.pending = self.pending, []
+        if not items:
+            return []
+        kinds = list(self.is_float)
+        try:
+            parts, run = [], []
+            for it in items + [None]:
+                batch = isinstance(it, ColumnBatch)
+                if run and (it is None or batch):
+                    parts.append(self._rec_columns(run, kinds))
+                    run = []
+                if it is None:
+                    break
+                if batch:
+                    if it.n:
+                        parts.append(self._cb_columns(it, kinds))
+                else:
+                    run.append(it)
+            if not parts:
+                return []
+            dev = torch.device(self.device)
+            to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64))  # noqa: E731
+                                if isinstance(x, np.ndarray) else x).to(dev)
+            cols = [torch.cat([to_dev(p[c]) for p in parts]) for c in range(len(parts[0]))]
+            keys, ts = cols[:2]
+            kmax, tmin, tmax = torch.stack([keys.max(), ts.min(), ts.max()]).tolist()
+            if kmax >= self.dense_limit:
+                raise TypeError("key beyond the dense table")
+            if tmin == LONG_MIN:
+                raise _NoTimestamp("a record without an event timestamp")
+            self._check_ts(tmin, tmax)
+        except TypeError as e:
+            # Unsupported data for the native path: the exact host operator, while no native
+            # state exists yet.
+            if self._has_state():
+                if isinstance(e, _NoTimestamp):
+                    raise ValueError(f"{self.fn_name}: a record without an event "
+                                     "timestamp") from None
+                raise
+            self._to_fallback()
+            return self.fallback.process(expand_columns(items))
+        self.is_float = kinds
+        return self._accept(cols, tmin, tmax)
+
+
+class NativeTimeoutOp(_NativeKeyedRuleOp):
     """``stream.key_by(p).process(CountWithTimeout(timeout))`` on the device timer operator
     (runtime/timeout_operator.py; planner._lower_keyed_process). One input: records, host and
     device column batches are buffered until a watermark or the end of the pass; the watermark
@@ -2477,6 +2533,7 @@ class NativeTimeoutOp(_NativeTwoSidedOp):
     afterwards."""
 
     name = "KeyedProcess(native timeout)"
+    fn_name = "CountWithTimeout"
 
     def __init__(self, *, fn, key_pos: int, device: str, fallback_factory,
                  dense_limit: int = 1 << 26):
@@ -2494,7 +2551,7 @@ class NativeTimeoutOp(_NativeTwoSidedOp):
                                        dense_limit=self.dense_limit)
         self.op.wm = self.wm  # a deadline at or below it fires at the next watermark
 
-    def _rec_columns(self, recs: list):
+    def _rec_columns(self, recs: list, kinds: list):
         kp = self.key_pos
         kid = np.empty(len(recs), dtype=np.int64)
         tsa = np.empty(len(recs), dtype=np.int64)
@@ -2506,7 +2563,7 @@ class NativeTimeoutOp(_NativeTwoSidedOp):
             tsa[i] = r.ts
         return kid, tsa
 
-    def _cb_columns(self, cb: ColumnBatch):
+    def _cb_columns(self, cb: ColumnBatch, kinds: list):
         if isinstance(cb, DeviceColumnBatch) and torch.device(self.device).type != "cuda":
             cb = cb.host()  # no engine on the batch's device: host columns
         if cb.scalar or len(cb.kinds) <= self.key_pos:
@@ -2515,51 +2572,14 @@ class NativeTimeoutOp(_NativeTwoSidedOp):
             raise _NoTimestamp("a batch without event timestamps")
         return self._batch_keys(cb, self.key_pos), cb.ts[:cb.n]
 
-    def _flush(self) -> list:
-        items, self.pending = self.pending, []
-        if not items:
-            return []
-        try:
-            parts, run = [], []
-            for it in items + [None]:
-                batch = isinstance(it, ColumnBatch)
-                if run and (it is None or batch):
-                    parts.append(self._rec_columns(run))
-                    run = []
-                if it is None:
-                    break
-                if batch:
-                    if it.n:
-                        parts.append(self._cb_columns(it))
-                else:
-                    run.append(it)
-            if not parts:
-                return []
-            dev = torch.device(self.device)
-            to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64))  # noqa: E731
-                                if isinstance(x, np.ndarray) else x).to(dev)
-            keys = torch.cat([to_dev(p[0]) for p in parts])
-            ts = torch.cat([to_dev(p[1]) for p in parts])
-            kmax, tmin, tmax = torch.stack([keys.max(), ts.min(), ts.max()]).tolist()
-            if kmax >= self.dense_limit:
-                raise TypeError("key beyond the dense table")
-            if tmin == LONG_MIN:
-                raise _NoTimestamp("a record without an event timestamp")
-            if tmax >= LONG_MAX - self.timeout:
-                raise TypeError("timestamp + timeout reaches INT64_MAX")
-        except TypeError as e:
-            # Unsupported data for the native path: the exact host operator, while no native
-            # state exists yet.
-            if self.op is not None:
-                if isinstance(e, _NoTimestamp):
-                    raise ValueError("CountWithTimeout: a record without an event "
-                                     "timestamp") from None
-                raise
-            self._to_fallback()
-            return self.fallback.process(expand_columns(items))
+    def _check_ts(self, tmin: int, tmax: int) -> None:
+        if tmax >= LONG_MAX - self.timeout:
+            raise TypeError("timestamp + timeout reaches INT64_MAX")
+
+    def _accept(self, cols, tmin: int, tmax: int) -> list:
         if self.op is None:
             self._build()
-        self.op.process(keys, ts)
+        self.op.process(*cols)
         return []
 
     def _on_watermark(self, wm: int) -> list:
@@ -2584,7 +2604,7 @@ class NativeTimeoutOp(_NativeTwoSidedOp):
         super().restore(snap)
 
 
-class NativeSustainOp(_NativeTwoSidedOp):
+class NativeSustainOp(_NativeKeyedRuleOp):
     """``stream.key_by(p).process(SustainedAlert(field, when, threshold, for_))`` on the device
     operator (runtime/sustain_operator.py; planner._lower_keyed_process). One input: records,
     host and device column batches are buffered until a watermark or the end of the pass and
@@ -2681,49 +2701,12 @@ class NativeSustainOp(_NativeTwoSidedOp):
                 .view(np.int64)
         return self._batch_keys(cb, kp), cb.ts[:cb.n], bits
 
-    def _flush(self) -> list:
-        items, self.pending = self.pending, []
-        if not items:
-            return []
-        kinds = list(self.is_float)
-        try:
-            parts, run = [], []
-            for it in items + [None]:
-                batch = isinstance(it, ColumnBatch)
-                if run and (it is None or batch):
-                    parts.append(self._rec_columns(run, kinds))
-                    run = []
-                if it is None:
-                    break
-                if batch:
-                    if it.n:
-                        parts.append(self._cb_columns(it, kinds))
-                else:
-                    run.append(it)
-            if not parts:
-                return []
-            dev = torch.device(self.device)
-            to_dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64))  # noqa: E731
-                                if isinstance(x, np.ndarray) else x).to(dev)
-            keys, ts, bits = (torch.cat([to_dev(p[c]) for p in parts]) for c in range(3))
-            kmax, tmin, tmax = torch.stack([keys.max(), ts.min(), ts.max()]).tolist()
-            if kmax >= self.dense_limit:
-                raise TypeError("key beyond the dense table")
-            if tmin == LONG_MIN:
-                raise _NoTimestamp("a record without an event timestamp")
-            if tmin <= -(1 << 62) or tmax >= 1 << 62:
-                raise TypeError("a timestamp at or beyond 2**62")
-        except TypeError as e:
-            # Unsupported data for the native path: the exact host operator, while no native
-            # state exists yet.
-            if self._has_state():
-                if isinstance(e, _NoTimestamp):
-                    raise ValueError(f"{self.fn_name}: a record without an event "
-                                     "timestamp") from None
-                raise
-            self._to_fallback()
-            return self.fallback.process(expand_columns(items))
-        self.is_float = kinds
+    def _check_ts(self, tmin: int, tmax: int) -> None:
+        if tmin <= -(1 << 62) or tmax >= 1 << 62:
+            raise TypeError("a timestamp at or beyond 2**62")
+
+    def _accept(self, cols, tmin: int, tmax: int) -> list:
+        keys, ts, bits = cols
         if self.ordered:
             if self.buf is None:
                 self._build_buffer()

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from ..ops import kernels as K
+from .rule_operator import metrics_meta
 from .window_operator import OperatorMetrics
 
 
@@ -126,9 +127,7 @@ class KeyedTimeoutOperator:
         kg = (K.keygroups(torch.from_numpy(ids), max_parallelism=128).numpy()
               if ids.size else np.zeros(0, np.int32))
         meta = {"kind": "count_timeout", "timeout": self.timeout, "wm": self.wm,
-                "metrics": {"num_records_in": self.metrics.num_records_in,
-                            "num_records_out": self.metrics.num_records_out,
-                            "num_fires": self.metrics.num_fires}}
+                "metrics": metrics_meta(self.metrics)}
         return OperatorSnapshot(kg, {"key": ids, "count": count, "last": last, "deadline": dl},
                                 meta)
 
