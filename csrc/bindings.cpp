@@ -181,6 +181,9 @@ FirePlan make_fire(py::dict d) {
     p.list_n = reinterpret_cast<const uint32_t*>(d["list_n"].cast<intptr_t>());
     if (!p.list_n) throw std::invalid_argument("slot list needs list_n");
   }
+  // Fused re-firing only (FirePlan.clear_mark): the touched-slot marks, one uint32 per slot.
+  if (d.contains("clear_mark") && d["clear_mark"].cast<intptr_t>())
+    p.clear_mark = reinterpret_cast<uint32_t*>(d["clear_mark"].cast<intptr_t>());
   py::tuple m = d["map"].cast<py::tuple>();
   py::tuple f = d["filt"].cast<py::tuple>();
   p.map = make_prog(m[0].cast<std::vector<int32_t>>(), m[1].cast<std::vector<double>>());
