@@ -4,35 +4,24 @@
 //
 // The expand is output-centric: a workgroup owns kJoinTile consecutive output positions, finds
 // the matched segments that overlap them by two binary searches in the plan's (strictly
-// increasing) first-pair column and keeps their tile-relative starts in LDS. A hot key's millions
-// of pairs are thus spread over as many workgroups as it has tiles, and thousands of small keys
-// share one. Every lane writes two consecutive positions per column with one 16-byte store; a
-// wave covers 128 consecutive positions (1 KiB per column and store). No atomics and no device
+// increasing) first-pair column and keeps their tile-relative starts in LDS (the tile frame,
+// csrc/pair_expand.h, which the interval join's expand shares). A hot key's millions of pairs
+// are thus spread over as many workgroups as it has tiles, and thousands of small keys share
+// one. Every lane writes two consecutive positions per column with one 16-byte store; a wave
+// covers 128 consecutive positions (1 KiB per column and store). No atomics and no device
 // counter: every position is known from the scan.
 #include <hip/hip_runtime.h>
 
 #include <stdexcept>
 #include <string>
 
+#include "mxs_hip_util.h"
 #include "mxs_join.h"
-#include "mxs_blockscan.h"
+#include "pair_expand.h"
+#include "pair_scan.h"
 
 namespace mxs {
 namespace {
-
-#define JOIN_CHECK(x)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
-int grid_of(int64_t n, int per_block, int cap) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < cap ? g : cap);
-}
 
 __device__ __forceinline__ int64_t seg_len(const int64_t* __restrict__ heads, int64_t nseg,
                                            int64_t total, int64_t i) {
@@ -60,119 +49,40 @@ __global__ __launch_bounds__(256) void join_match_kernel(
   }
 }
 
-// ---- scan (64-bit, saturating; the tiles + one-workgroup tile scan of lw_scan) ---------------
-constexpr int kScanThreads = 1024;
-constexpr int kScanPer = kJoinScanTile / kScanThreads;  // 4 segments per thread
+// ---- scan (csrc/pair_scan.h over the left segments: 64-bit, saturating) -----------------------
+struct JoinScan {
+  using Add = SatAdd;
+  const uint64_t* cnt;
+  const int64_t *match, *lkeys, *lheads;
+  int64_t kl;
+  const int64_t* rheads;
+  int64_t kr, rtotal;
+  int64_t *pair_off, *plan, *meta;
 
-// Pass 1: per tile, the pair total and the number of matched (non-empty) segments.
-__global__ __launch_bounds__(kScanThreads) void join_tile_sums_kernel(
-    const uint64_t* __restrict__ cnt, int64_t kl, uint64_t* __restrict__ tsum,
-    uint32_t* __restrict__ tne) {
-  __shared__ uint64_t ws[16];
-  __shared__ uint32_t wn[16];
-  __shared__ uint64_t tot;
-  __shared__ uint32_t totn;
-  const int64_t k0 = (int64_t)blockIdx.x * kJoinScanTile + (int64_t)threadIdx.x * kScanPer;
-  uint64_t s = 0;
-  uint32_t ne = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    const uint64_t c = k0 + j < kl ? cnt[k0 + j] : 0ull;
-    s = join_sat_add(s, c);
-    ne += c ? 1u : 0u;
+  __device__ __forceinline__ uint64_t count(int64_t i) const { return cnt[i]; }
+  __device__ __forceinline__ void element(int64_t i, uint64_t o) const {
+    pair_off[i] = (int64_t)o;
   }
-  block_excl_scan<uint64_t>(s, ws, &tot, SatAdd());
-  block_excl_scan<uint32_t>(ne, wn, &totn, Add32());
-  if (threadIdx.x == 0) {
-    tsum[blockIdx.x] = tot;
-    tne[blockIdx.x] = totn;
+  // the plan row of matched segment i
+  __device__ __forceinline__ void nonempty(int64_t i, int64_t h, uint64_t o) const {
+    const int64_t stride = kl + 1, rj = match[i];
+    plan[kJoinFirst * stride + h] = (int64_t)o;
+    plan[kJoinKey * stride + h] = lkeys[i];
+    plan[kJoinLs * stride + h] = lheads[i];
+    plan[kJoinRs * stride + h] = rheads[rj];
+    plan[kJoinNr * stride + h] = seg_len(rheads, kr, rtotal, rj);
   }
-}
-
-// Pass 2 (one workgroup): exclusive scan of the tile totals, kScanThreads tiles per round with a
-// carry, so any number of tiles; the totals P, m and the error word.
-__global__ __launch_bounds__(kScanThreads) void join_tile_scan_kernel(
-    uint64_t* __restrict__ tsum, uint32_t* __restrict__ tne, int64_t ntiles, int64_t kl,
-    int64_t* __restrict__ pair_off, int64_t* __restrict__ plan, int64_t* __restrict__ meta) {
-  __shared__ uint64_t ws[16];
-  __shared__ uint32_t wn[16];
-  __shared__ uint64_t tot;
-  __shared__ uint32_t totn;
-  uint64_t carry = 0;
-  uint32_t carry_n = 0;
-  for (int64_t base = 0; base < ntiles; base += kScanThreads) {
-    const int64_t t = base + threadIdx.x;
-    const uint64_t s = t < ntiles ? tsum[t] : 0ull;
-    const uint32_t e = t < ntiles ? tne[t] : 0u;
-    const uint64_t bs = block_excl_scan<uint64_t>(s, ws, &tot, SatAdd());
-    const uint32_t be = block_excl_scan<uint32_t>(e, wn, &totn, Add32());
-    if (t < ntiles) {
-      tsum[t] = join_sat_add(carry, bs);
-      tne[t] = carry_n + be;
-    }
-    carry = join_sat_add(carry, tot);
-    carry_n += totn;
-    __syncthreads();  // tot / totn are rewritten by the next round
+  // the totals P, m and the error word
+  __device__ __forceinline__ void finish(uint64_t P, uint32_t m) const {
+    pair_off[kl] = (int64_t)P;
+    plan[(int64_t)kJoinFirst * (kl + 1) + m] = (int64_t)P;
+    meta[kJoinP] = (int64_t)P;
+    meta[kJoinM] = (int64_t)m;
+    meta[kJoinErr] = P >= (uint64_t)kJoinMaxPairs ? 1 : 0;
   }
-  if (threadIdx.x == 0) {
-    pair_off[kl] = (int64_t)carry;
-    plan[(int64_t)kJoinFirst * (kl + 1) + carry_n] = (int64_t)carry;
-    meta[kJoinP] = (int64_t)carry;
-    meta[kJoinM] = (int64_t)carry_n;
-    meta[kJoinErr] = carry >= (uint64_t)kJoinMaxPairs ? 1 : 0;
-  }
-}
-
-// Pass 3: per tile, every segment's exclusive offset and the plan rows of the matched ones, in
-// segment order.
-__global__ __launch_bounds__(kScanThreads) void join_tile_write_kernel(
-    const uint64_t* __restrict__ cnt, const int64_t* __restrict__ match,
-    const int64_t* __restrict__ lkeys, const int64_t* __restrict__ lheads, int64_t kl,
-    const int64_t* __restrict__ rheads, int64_t kr, int64_t rtotal,
-    const uint64_t* __restrict__ tsum, const uint32_t* __restrict__ tne,
-    int64_t* __restrict__ pair_off, int64_t* __restrict__ plan) {
-  __shared__ uint64_t ws[16];
-  __shared__ uint32_t wn[16];
-  __shared__ uint64_t tot;
-  __shared__ uint32_t totn;
-  const int64_t k0 = (int64_t)blockIdx.x * kJoinScanTile + (int64_t)threadIdx.x * kScanPer;
-  uint64_t c[kScanPer];
-  uint64_t s = 0;
-  uint32_t ne = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    c[j] = k0 + j < kl ? cnt[k0 + j] : 0ull;
-    s = join_sat_add(s, c[j]);
-    ne += c[j] ? 1u : 0u;
-  }
-  uint64_t o = join_sat_add(tsum[blockIdx.x], block_excl_scan<uint64_t>(s, ws, &tot, SatAdd()));
-  int64_t h = (int64_t)tne[blockIdx.x] + block_excl_scan<uint32_t>(ne, wn, &totn, Add32());
-  const int64_t stride = kl + 1;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    const int64_t i = k0 + j;
-    if (i < kl) {
-      pair_off[i] = (int64_t)o;
-      if (c[j]) {
-        const int64_t rj = match[i];
-        plan[kJoinFirst * stride + h] = (int64_t)o;
-        plan[kJoinKey * stride + h] = lkeys[i];
-        plan[kJoinLs * stride + h] = lheads[i];
-        plan[kJoinRs * stride + h] = rheads[rj];
-        plan[kJoinNr * stride + h] = seg_len(rheads, kr, rtotal, rj);
-        ++h;
-      }
-    }
-    o = join_sat_add(o, c[j]);
-  }
-}
+};
 
 // ---- expand --------------------------------------------------------------------------------
-typedef long long ll2 __attribute__((ext_vector_type(2)));
-
-constexpr int kJoinStep = 2 * kJoinBlock;        // positions a workgroup covers per store round
-constexpr int kJoinRounds = kJoinTile / kJoinStep;
-
 // q = (a, b) advanced to a * nr + b + d (d < 2^31): one 32-bit division while everything fits.
 __device__ __forceinline__ void join_divmod(uint64_t q, uint64_t nr, uint64_t* a, uint64_t* b) {
   if (((q | nr) >> 32) == 0) {
@@ -188,64 +98,36 @@ __global__ __launch_bounds__(kJoinBlock) void join_expand_kernel(
     const int64_t* __restrict__ plan, int64_t stride, int64_t m, const uint64_t* __restrict__ lord,
     const uint64_t* __restrict__ rord, int64_t p0, int64_t p1, int64_t ntiles,
     int64_t* __restrict__ out_key, int64_t* __restrict__ out_l, int64_t* __restrict__ out_r) {
-  // rel[k]: the tile-relative first position of the tile's k-th segment (rel[0] = 0: the segment
-  // that owns the tile's first position started at or before it), rel[ns] = the tile's length.
-  __shared__ int32_t rel[kJoinTile + 1];
+  __shared__ int32_t rel[kJoinTile + 1];  // the tile's segment starts (pair_tile_begin)
   const int64_t* __restrict__ first = plan + kJoinFirst * stride;
   const int64_t* __restrict__ pkey = plan + kJoinKey * stride;
   const int64_t* __restrict__ pls = plan + kJoinLs * stride;
   const int64_t* __restrict__ prs = plan + kJoinRs * stride;
   const int64_t* __restrict__ pnr = plan + kJoinNr * stride;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t tb = p0 + tile * kJoinTile;
-    const int32_t len = (int32_t)(p1 - tb < kJoinTile ? p1 - tb : kJoinTile);
-    const int64_t te = tb + len;
-    // s0 = the last segment with first <= tb; s1 = the first segment after s0 with first >= te
-    // (first[m] = P >= te). Both searches are uniform over the workgroup.
-    int64_t lo = 0, hi = m;  // first[lo] <= tb < first[hi]
-    int64_t lo2 = 0, hi2 = m;  // first[lo2] < te <= first[hi2]
-    while (hi - lo > 1 || hi2 - lo2 > 1) {
-      if (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (first[mid] <= tb) lo = mid; else hi = mid;
-      }
-      if (hi2 - lo2 > 1) {
-        const int64_t mid = lo2 + ((hi2 - lo2) >> 1);
-        if (first[mid] < te) lo2 = mid; else hi2 = mid;
-      }
-    }
-    const int64_t s0 = lo;
-    const int32_t ns = (int32_t)(hi2 - s0);  // 1 <= ns <= len: offsets strictly increase
-    const int64_t qbase = tb - first[s0];    // pairs of segment s0 before the tile
-    for (int32_t k = threadIdx.x; k <= ns; k += kJoinBlock)
-      rel[k] = k == 0 ? 0 : (k == ns ? len : (int32_t)(first[s0 + k] - tb));
-    __syncthreads();
+    const PairTile t = pair_tile_begin(first, m, p0, p1, tile, rel);
+    const int64_t tb = t.tb, s0 = t.s0;
+    const int32_t len = t.len;
 
     int32_t k = -1, nxt = 0;  // the lane's segment of the tile and the start of the next one
     int64_t key = 0, ls = 0, rs = 0;
     uint64_t nr = 1, a = 0, b = 0;
 #pragma unroll 2
-    for (int r = 0; r < kJoinRounds; ++r) {
-      const int32_t pr = r * kJoinStep + 2 * (int32_t)threadIdx.x;
+    for (int r = 0; r < kPairRounds; ++r) {
+      const int32_t pr = r * kPairStep + 2 * (int32_t)threadIdx.x;
       if (pr >= len) break;
       if (pr >= nxt) {
-        // another segment: the last k' > k with rel[k'] <= pr (rel[k + 1] = nxt <= pr < rel[ns])
-        int32_t l2 = k + 1, h2 = ns;
-        while (h2 - l2 > 1) {
-          const int32_t mid = (l2 + h2) >> 1;
-          if (rel[mid] <= pr) l2 = mid; else h2 = mid;
-        }
-        k = l2;
+        k = pair_lane_row(rel, k, t.ns, pr);  // another segment
         nxt = rel[k + 1];
         key = pkey[s0 + k];
         ls = pls[s0 + k];
         rs = prs[s0 + k];
         nr = (uint64_t)pnr[s0 + k];
-        const uint64_t q = (uint64_t)(pr - rel[k]) + (k == 0 ? (uint64_t)qbase : 0ull);
+        const uint64_t q = (uint64_t)(pr - rel[k]) + (k == 0 ? (uint64_t)t.qbase : 0ull);
         join_divmod(q, nr, &a, &b);
       } else {
-        // the same segment, kJoinStep positions on: carry (a, b) forward
-        const uint64_t bb = b + kJoinStep;
+        // the same segment, kPairStep positions on: carry (a, b) forward
+        const uint64_t bb = b + kPairStep;
         if (bb < nr) {
           b = bb;
         } else {
@@ -294,13 +176,10 @@ void join_match(const JoinSide& l, const JoinSide& r, int64_t* match, uint64_t* 
   hipLaunchKernelGGL(join_match_kernel, dim3(grid_of(l.nseg, 256, 2048)), dim3(256), 0,
                      (hipStream_t)stream, l.keys, l.heads, l.nseg, l.total, r.keys, r.heads,
                      r.nseg, r.total, match, cnt);
-  JOIN_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
-int64_t join_scan_scratch_bytes(int64_t kl) {
-  const int64_t nt = (kl + kJoinScanTile - 1) / kJoinScanTile;
-  return nt * (int64_t)(sizeof(uint64_t) + sizeof(uint32_t)) + 64;
-}
+int64_t join_scan_scratch_bytes(int64_t kl) { return pair_scan_scratch_bytes(kl); }
 
 void join_scan(const JoinSide& l, const JoinSide& r, const int64_t* match, const uint64_t* cnt,
                void* scratch, int64_t* pair_off, int64_t* plan, int64_t* meta, intptr_t stream) {
@@ -308,19 +187,9 @@ void join_scan(const JoinSide& l, const JoinSide& r, const int64_t* match, const
   if (kl < 0) throw std::invalid_argument("join_scan: negative segment count");
   const int64_t nt = (kl + kJoinScanTile - 1) / kJoinScanTile;
   if (nt > 0x7FFFFFFFll) throw std::invalid_argument("join_scan: too many segments");
-  uint64_t* tsum = reinterpret_cast<uint64_t*>(scratch);
-  uint32_t* tne = reinterpret_cast<uint32_t*>(tsum + nt);
-  hipStream_t s = (hipStream_t)stream;
-  if (nt)
-    hipLaunchKernelGGL(join_tile_sums_kernel, dim3((unsigned)nt), dim3(kScanThreads), 0, s, cnt,
-                       kl, tsum, tne);
-  hipLaunchKernelGGL(join_tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, tsum, tne, nt, kl,
-                     pair_off, plan, meta);
-  if (nt)
-    hipLaunchKernelGGL(join_tile_write_kernel, dim3((unsigned)nt), dim3(kScanThreads), 0, s, cnt,
-                       match, l.keys, l.heads, kl, r.heads, r.nseg, r.total, tsum, tne, pair_off,
-                       plan);
-  JOIN_CHECK(hipGetLastError());
+  const JoinScan p = {cnt, match, l.keys, l.heads, kl, r.heads, r.nseg, r.total,
+                      pair_off, plan, meta};
+  pair_scan_launch(p, kl, scratch, (hipStream_t)stream);
 }
 
 void join_expand(const int64_t* plan, int64_t kl, int64_t m, int64_t P, const uint64_t* lord,
@@ -338,7 +207,7 @@ void join_expand(const int64_t* plan, int64_t kl, int64_t m, int64_t P, const ui
   hipLaunchKernelGGL(join_expand_kernel, dim3(grid_of(ntiles, 1, 2048)), dim3(kJoinBlock), 0,
                      (hipStream_t)stream, plan, kl + 1, m, lord, rord, p0, p1, ntiles, out_key,
                      out_l, out_r);
-  JOIN_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

@@ -28,18 +28,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "mxs_hip_util.h"
 #include "mxs_kernels.h"
 
 namespace mxs {
 namespace {
-
-#define HIP_CHECK(x)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
 
 constexpr int kWave = 64;
 // Partition variants (scripts/kbench.py A/B, profiles/): 0 plain scatter, 1 + non-temporal
@@ -5270,13 +5263,13 @@ void gen_events(uint64_t* keys, int64_t* ts, uint64_t* vals, int64_t n, uint64_t
                      (hipStream_t)stream, keys, ts, vals, n, seed, stream_id, idx0, nkeys, ts_base,
                      (double)ts_span / (double)n, (uint64_t)(disorder + 1), val_lo,
                      (uint64_t)(val_span > 0 ? val_span : 0), mode, zipf_s, key_base);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void step_begin(uint32_t* cursor, int nb, int64_t* stats, intptr_t stream) {
   hipLaunchKernelGGL(step_begin_kernel, dim3(grid_for(nb, 256, 64)), dim3(256), 0,
                      (hipStream_t)stream, cursor, nb, stats);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void step_finish(const int64_t* stats, int64_t* local_maxts, int64_t bound, int32_t event_mode,
@@ -5287,14 +5280,14 @@ void step_finish(const int64_t* stats, int64_t* local_maxts, int64_t bound, int3
                      local_maxts, bound, event_mode, proc_now, red, flags, idle, host_red,
                      fill_word && cursor ? 1 : 0, cursor, nb, next_stats ? next_cursor : nullptr,
                      next_cursor ? next_stats : nullptr);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void combine_check(const uint32_t* flags, const uint32_t* counts, int nb, int64_t* chk,
                    intptr_t stream) {
   hipLaunchKernelGGL(combine_check_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, flags,
                      counts, nb, chk);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void bucket_repack(const uint64_t* src, const uint32_t* counts, int nb, uint32_t src_cap,
@@ -5302,13 +5295,13 @@ void bucket_repack(const uint64_t* src, const uint32_t* counts, int nb, uint32_t
   if (nb <= 0) return;
   hipLaunchKernelGGL(bucket_repack_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, src,
                      counts, src_cap, dst_cap, words, dst, (unsigned long long*)xstat);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void neg_max_u32(const uint32_t* counts, int nb, int64_t* out, intptr_t stream) {
   hipLaunchKernelGGL(neg_max_u32_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, counts, nb,
                      out);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void widen_i32(const int32_t* in, int64_t n, int64_t* out, intptr_t stream) {
@@ -5316,7 +5309,7 @@ void widen_i32(const int32_t* in, int64_t n, int64_t* out, intptr_t stream) {
   const int64_t blocks = std::min<int64_t>(8192, (n + 255) / 256);
   hipLaunchKernelGGL(widen_i32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in,
                      n, out);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void zero_panes(void* acc, int acc_bytes, uint32_t* cnt, uint8_t* dirty, int64_t so, int64_t n,
@@ -5328,16 +5321,16 @@ void zero_panes(void* acc, int acc_bytes, uint32_t* cnt, uint8_t* dirty, int64_t
   uint8_t* c = dirty + so;
   const int64_t na = n * acc_bytes / 16, nb = n * 4 / 16, nc = n / 16;
   if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) || (n & 15)) {
-    HIP_CHECK(hipMemsetAsync(a, 0, n * acc_bytes, (hipStream_t)stream));
-    HIP_CHECK(hipMemsetAsync(b, 0, n * 4, (hipStream_t)stream));
-    HIP_CHECK(hipMemsetAsync(c, 0, n, (hipStream_t)stream));
+    MXS_HIP_CHECK(hipMemsetAsync(a, 0, n * acc_bytes, (hipStream_t)stream));
+    MXS_HIP_CHECK(hipMemsetAsync(b, 0, n * 4, (hipStream_t)stream));
+    MXS_HIP_CHECK(hipMemsetAsync(c, 0, n, (hipStream_t)stream));
     return;
   }
   const int64_t tot = na + nb + nc;
   const int64_t blocks = std::min<int64_t>(2048, (tot + 255) / 256);
   hipLaunchKernelGGL(zero3_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                      (uint4*)a, na, (uint4*)b, nb, (uint4*)c, nc);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void fill_u64(uint64_t* p, int64_t n, uint64_t v, intptr_t stream) {
@@ -5345,7 +5338,7 @@ void fill_u64(uint64_t* p, int64_t n, uint64_t v, intptr_t stream) {
   const int64_t blocks = std::min<int64_t>(4096, (n + 255) / 256);
   hipLaunchKernelGGL(fill_u64_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p,
                      n, v);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 int getenv_int(const char* name, int def) {
@@ -5367,23 +5360,23 @@ void launch_compact(const uint64_t* keys, const int64_t* ts, const uint64_t* val
       auto k8 = partition_compact_kernel<1, 8, ONE, RB, K32, PAIR>;
       static bool attr8 = false;
       if (!attr8) {
-        HIP_CHECK(hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)compact_lds_rb(8, 8)));
+        MXS_HIP_CHECK(hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)compact_lds_rb(8, 8)));
         attr8 = true;
       }
       const size_t lds8 = compact_lds_rb(8, 8) - (ONE ? (size_t)kKgLdsMax * 4 : 0);
       hipLaunchKernelGGL(k8, dim3(blocks), dim3(1024), lds8, (hipStream_t)stream, keys, ts, vals,
                          jhash_tab, n, chunk, plan, kg_dest, cursor, reinterpret_cast<RecC*>(out),
                          stats, late_idx, late_cap);
-      HIP_CHECK(hipGetLastError());
+      MXS_HIP_CHECK(hipGetLastError());
       return;
     }
   }
   auto kfn = partition_compact_kernel<1, kCUProd, ONE, RB, K32, PAIR>;
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)compact_lds(kCUProd)));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)compact_lds(kCUProd)));
     attr = true;
   }
   // One rank: no key-group hashing and no LDS kg table.
@@ -5391,7 +5384,7 @@ void launch_compact(const uint64_t* keys, const int64_t* ts, const uint64_t* val
   hipLaunchKernelGGL(kfn, dim3(blocks), dim3(1024), lds, (hipStream_t)stream, keys, ts, vals,
                      jhash_tab, n, chunk, plan, kg_dest, cursor, reinterpret_cast<RecC*>(out),
                      stats, late_idx, late_cap);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 static const bool kPairEnv = getenv_int("MXS_PAIR", 1) != 0;  // A/B knobs (profiles)
@@ -5551,8 +5544,8 @@ void launch_onepass(const uint64_t* keys, const int64_t* ts, const uint64_t* val
     auto kfn = partition_onepass_kernel<1, RU, K32_, PAIR_>;                                    \
     static bool attr = false;                                                                   \
     if (!attr) {                                                                                \
-      HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)onepass_lds(RU)));                                     \
+      MXS_HIP_CHECK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                        (int)onepass_lds(RU)));                                 \
       attr = true;                                                                              \
     }                                                                                           \
     hipLaunchKernelGGL(kfn, dim3(blocks), dim3(1024), onepass_lds(RU), (hipStream_t)stream,      \
@@ -5567,7 +5560,7 @@ void launch_onepass(const uint64_t* keys, const int64_t* ts, const uint64_t* val
     else MXS_ONEPASS(false, false);
   }
 #undef MXS_ONEPASS
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 template <bool ONE, int RB>
@@ -5640,13 +5633,13 @@ void partition(const uint64_t* keys, const int64_t* ts, const uint64_t* vals,
       pc.nsub_log2 = plan.nsub_log2 - L;
       pc.bucket_cap = plan.bucket_cap << L;
       hipStream_t st = (hipStream_t)stream;
-      HIP_CHECK(hipMemsetAsync(plan.scratch_cursor, 0, sizeof(uint32_t) * (nb >> L), st));
+      MXS_HIP_CHECK(hipMemsetAsync(plan.scratch_cursor, 0, sizeof(uint32_t) * (nb >> L), st));
       dispatch_compact<true, 8>(keys, ts, vals, jhash_tab, n, pc, kg_dest, plan.scratch_cursor,
                                 (Rec*)plan.scratch, stats, late_idx, late_cap, stream);
       hipLaunchKernelGGL(partition_split_kernel<8>, dim3(nb >> L), dim3(kSplitThreads), 0, st,
                          (const void*)plan.scratch, plan.scratch_cursor, pc.bucket_cap, plan, L,
                          cursor, (void*)out, stats);
-      HIP_CHECK(hipGetLastError());
+      MXS_HIP_CHECK(hipGetLastError());
       return;
     }
     if (nb > kCMaxNb) {
@@ -5673,7 +5666,7 @@ void partition(const uint64_t* keys, const int64_t* ts, const uint64_t* vals,
     pc.bucket_cap = plan.bucket_cap << L;
     if (pc.nsub_log2 < 0) throw std::invalid_argument("two-level partition: too few sub-tables");
     hipStream_t st = (hipStream_t)stream;
-    HIP_CHECK(hipMemsetAsync(plan.scratch_cursor, 0, sizeof(uint32_t) * (nb >> L), st));
+    MXS_HIP_CHECK(hipMemsetAsync(plan.scratch_cursor, 0, sizeof(uint32_t) * (nb >> L), st));
     if (plan.nranks == 1)
       dispatch_compact<true, 16>(keys, ts, vals, jhash_tab, n, pc, kg_dest, plan.scratch_cursor,
                                  (Rec*)plan.scratch, stats, late_idx, late_cap, stream);
@@ -5683,7 +5676,7 @@ void partition(const uint64_t* keys, const int64_t* ts, const uint64_t* vals,
     hipLaunchKernelGGL(partition_split_kernel<16>, dim3(nb >> L), dim3(kSplitThreads), 0, st,
                        (const void*)plan.scratch, plan.scratch_cursor, pc.bucket_cap, plan, L,
                        cursor, (void*)out, stats);
-    HIP_CHECK(hipGetLastError());
+    MXS_HIP_CHECK(hipGetLastError());
     return;
   }
   if (plan.rec_words == 2 && nb <= kCMaxNb && (uint64_t)nb * plan.bucket_cap < (1ull << 32)) {
@@ -5710,13 +5703,13 @@ void partition(const uint64_t* keys, const int64_t* ts, const uint64_t* vals,
     pc.bucket_cap = plan.bucket_cap << L;
     if (pc.nsub_log2 < 0) throw std::invalid_argument("two-level partition: too few sub-tables");
     hipStream_t st = (hipStream_t)stream;
-    HIP_CHECK(hipMemsetAsync(plan.scratch_cursor, 0, sizeof(uint32_t) * (nb >> L), st));
+    MXS_HIP_CHECK(hipMemsetAsync(plan.scratch_cursor, 0, sizeof(uint32_t) * (nb >> L), st));
     partition_variant(keys, ts, vals, jhash_tab, n, pc, kg_dest, plan.scratch_cursor,
                       (Rec*)plan.scratch, stats, late_idx, late_cap, stream, 5);
     hipLaunchKernelGGL(partition_split_kernel<24>, dim3(nb >> L), dim3(kSplitThreads), 0, st,
                        (const void*)plan.scratch, plan.scratch_cursor, pc.bucket_cap, plan, L,
                        cursor, (void*)out, stats);
-    HIP_CHECK(hipGetLastError());
+    MXS_HIP_CHECK(hipGetLastError());
     return;
   }
   // Write-combined staged scatter when the LDS carry buffers fit (<= 512 buckets); otherwise
@@ -5772,8 +5765,8 @@ void partition_variant(const uint64_t* keys, const int64_t* ts, const uint64_t* 
   case VV: {                                                                                  \
     static bool attr = false;                                                                 \
     if (!attr) {                                                                              \
-      HIP_CHECK(hipFuncSetAttribute((const void*)partition_kernel<VV>,                         \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));   \
+      MXS_HIP_CHECK(hipFuncSetAttribute((const void*)partition_kernel<VV>,                    \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); \
       attr = true;                                                                            \
     }                                                                                         \
     hipLaunchKernelGGL(partition_kernel<VV>, dim3(blocks), dim3(1024), lds, st, keys, ts, vals, \
@@ -5786,8 +5779,8 @@ void partition_variant(const uint64_t* keys, const int64_t* ts, const uint64_t* 
     if (nb > kStageMaxNb) throw std::runtime_error("staged partition needs <= 512 buckets");  \
     static bool attr = false;                                                                 \
     if (!attr) {                                                                              \
-      HIP_CHECK(hipFuncSetAttribute((const void*)partition_staged_kernel<TV>,                  \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStagedLds)); \
+      MXS_HIP_CHECK(hipFuncSetAttribute((const void*)partition_staged_kernel<TV>,             \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStagedLds)); \
       attr = true;                                                                            \
     }                                                                                         \
     hipLaunchKernelGGL(partition_staged_kernel<TV>, dim3(blocks), dim3(1024), kStagedLds, st,   \
@@ -5800,9 +5793,9 @@ void partition_variant(const uint64_t* keys, const int64_t* ts, const uint64_t* 
     if (plan.rec_words != 2 || nb > kCMaxNb) throw std::runtime_error("compact variant: plan"); \
     static bool attr = false;                                                                 \
     if (!attr) {                                                                              \
-      HIP_CHECK(hipFuncSetAttribute((const void*)partition_compact_kernel<1, CUV>,             \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,                \
-                                    (int)compact_lds(CUV)));                                   \
+      MXS_HIP_CHECK(hipFuncSetAttribute((const void*)partition_compact_kernel<1, CUV>,        \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                                        (int)compact_lds(CUV)));                              \
       attr = true;                                                                            \
     }                                                                                         \
     const int cb = grid_for(n, EPB, 2048);                                                    \
@@ -5825,7 +5818,7 @@ void partition_variant(const uint64_t* keys, const int64_t* ts, const uint64_t* 
 #undef MXS_PART
 #undef MXS_PART_STAGED
 #undef MXS_PART_COMPACT
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 // Packed (sum, count) accumulators apply: integer sum/avg over 16-byte records, raw events
@@ -5854,8 +5847,8 @@ static void launch_agg_v(const Rec* recs, const uint32_t* counts, const AggPlan&
   if (lds > kAggDynMax) throw std::runtime_error("window_agg: LDS image exceeds 160 KiB");
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)window_agg_kernel<AGG, RW, PK, DENSE, DET, V, LEAN>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAggDynMax));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_agg_kernel<AGG, RW, PK, DENSE, DET, V, LEAN>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAggDynMax));
     attr = true;
   }
   // Split only what the kernel's atomic merge supports: dense ids (no LDS key table to share),
@@ -5966,7 +5959,7 @@ void window_agg(const Rec* recs, const uint32_t* counts, const AggPlan& plan, ui
 #undef MXS_A
     default: throw std::runtime_error("window_agg: unknown aggregate");
   }
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 // Tiered firing: combine rows per key into a global open-addressing table with atomics (see
@@ -6059,15 +6052,15 @@ void window_fire(const uint64_t* keys_g, const uint64_t* acc_g, const uint32_t* 
   if (lds > 160 * 1024) throw std::runtime_error("window_fire: epilogue stack too deep for LDS");
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)window_fire_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_fire_kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   hipLaunchKernelGGL(window_fire_kernel, dim3(grid_for(plan.nslots, kFireThreads * kFireU, 1024)),
                      dim3(kFireThreads), lds,
                      (hipStream_t)stream, keys_g, acc_g, cnt_g, dirty_g, plan, out_keys, out_vals,
                      out_raw, out_cnt, out_n);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void window_fire_many(const uint64_t* keys_g, const uint64_t* acc_g, const uint32_t* cnt_g,
@@ -6080,7 +6073,7 @@ void window_fire_many(const uint64_t* keys_g, const uint64_t* acc_g, const uint3
   const int depth = base.map.depth > base.filt.depth ? base.map.depth : base.filt.depth;
   const size_t lds = (size_t)(kExprVars + depth) * kFireMultiThreads * sizeof(double) + 8 * 4;
   hipStream_t s = (hipStream_t)stream;
-  HIP_CHECK(hipMemsetAsync(st.win_n, 0, sizeof(uint32_t) * k, s));
+  MXS_HIP_CHECK(hipMemsetAsync(st.win_n, 0, sizeof(uint32_t) * k, s));
   const int64_t nvisit = base.nslots;
   const bool big = nvisit >= 65536;
   const int gx = grid_for(nvisit, kFireMultiThreads * (big ? 4 : 1), big ? 256 : 1024);
@@ -6094,12 +6087,12 @@ void window_fire_many(const uint64_t* keys_g, const uint64_t* acc_g, const uint3
     else
       hipLaunchKernelGGL(window_fire_multi_kernel<1>, dim3(gx, pack.n), dim3(kFireMultiThreads),
                          lds, s, keys_g, acc_g, cnt_g, dirty_g, base, pack, w0, st);
-    HIP_CHECK(hipGetLastError());
+    MXS_HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(fire_pack_kernel, dim3(grid_for(nvisit, 256 * 4, 64), k), dim3(256), 0, s,
                      st, k, base.key32, out_keys, out_vals, out_raw, out_cnt, bounds, out_n,
                      nullptr);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 bool window_refire_many(const uint64_t* keys_g, const uint64_t* acc_g, const uint32_t* cnt_g,
@@ -6123,7 +6116,7 @@ bool window_refire_many(const uint64_t* keys_g, const uint64_t* acc_g, const uin
   const int depth = base.map.depth > base.filt.depth ? base.map.depth : base.filt.depth;
   const size_t lds = (size_t)(kExprVars + depth) * kRefireThreads * sizeof(double) + 8 * 4;
   hipStream_t s = (hipStream_t)stream;
-  HIP_CHECK(hipMemsetAsync(st.win_n, 0, sizeof(uint32_t) * k, s));
+  MXS_HIP_CHECK(hipMemsetAsync(st.win_n, 0, sizeof(uint32_t) * k, s));
   FireWinPack pack{};
   pack.n = k;
   for (int i = 0; i < k; ++i) pack.w[i] = wins[i];
@@ -6133,11 +6126,11 @@ bool window_refire_many(const uint64_t* keys_g, const uint64_t* acc_g, const uin
                      dim3(kRefireThreads), lds, s, keys_g, acc_g, cnt_g,
                      const_cast<uint8_t*>(dirty_g), base, pack, u0,
                      (int)(u1 - u0), dmask, st);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(fire_pack_kernel, dim3(grid_for(base.nslots / k, 256 * 4, 64), k), dim3(256),
                      0, s, st, k, base.key32, out_keys, out_vals, out_raw, out_cnt, bounds, out_n,
                      ovf);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   return true;
 }
 
@@ -6148,7 +6141,7 @@ void direct_agg_probe(const uint64_t* keys, const int64_t* ts, const uint64_t* v
   hipLaunchKernelGGL(direct_agg_probe_kernel, dim3(grid > 0 ? grid : grid_for(n, 256 * 4, 16384)),
                      dim3(256), 0, (hipStream_t)stream, keys, ts, vals, n, tbase, pane, ring,
                      nslots, mul, bits, pane_base, acc_g, cnt_g, mode, sink);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void window_compact(uint64_t* keys_g, uint64_t* acc_g, uint32_t* cnt_g, uint8_t* dirty_g,
@@ -6161,15 +6154,15 @@ void window_compact(uint64_t* keys_g, uint64_t* acc_g, uint32_t* cnt_g, uint8_t*
   const size_t lds = cap * (8 * 3 + 4 * 2 + 1) + 32;
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)window_compact_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_compact_kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   const int64_t nslots = (int64_t)nsub << cap_log2;
   hipLaunchKernelGGL(window_compact_kernel, dim3(nsub), dim3(1024), lds, (hipStream_t)stream,
                      keys_g, acc_g, cnt_g, dirty_g, cap_log2, ring, nslots, p_lo, np, cutoff, out,
                      occupancy);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void window_rows_pane_sort(const uint64_t* key, const int64_t* pane, const uint64_t* acc,
@@ -6180,7 +6173,7 @@ void window_rows_pane_sort(const uint64_t* key, const int64_t* pane, const uint6
     throw std::invalid_argument("window_rows_pane_sort: 1..64 panes");
   hipStream_t s = (hipStream_t)stream;
   // counts[0, 64): rows per pane (read by the host with the rows), [64, 128): scatter cursors
-  HIP_CHECK(hipMemsetAsync(counts, 0, 2 * kPaneSortMax * sizeof(uint32_t), s));
+  MXS_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * kPaneSortMax * sizeof(uint32_t), s));
   if (cap == 0) return;
   const uint32_t want = (cap + 256 * 8 - 1) / (256 * 8);
   const uint32_t blocks = want < 2048 ? (want ? want : 1) : 2048;
@@ -6189,7 +6182,7 @@ void window_rows_pane_sort(const uint64_t* key, const int64_t* pane, const uint6
   hipLaunchKernelGGL(pane_sort_scatter_kernel, dim3(blocks), dim3(256), 0, s, key, pane, acc, cnt,
                      dirty, n_dev, cap, p_lo, np, counts, counts + kPaneSortMax, okey, oacc, ocnt,
                      odirty);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void dirty_clear(const uint32_t* list, const uint32_t* list_n, uint32_t list_cap, int ring,
@@ -6200,7 +6193,7 @@ void dirty_clear(const uint32_t* list, const uint32_t* list_n, uint32_t list_cap
   hipLaunchKernelGGL(dirty_clear_kernel, dim3(grid_for(list_cap, 256, 4096)), dim3(256), 0,
                      (hipStream_t)stream, list, list_n, list_cap, ring, nslots, dirty_g, slot_mark,
                      p_lo, np, dacc, dcnt);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void scatter_partials(const uint64_t* keys, const uint64_t* acc, const uint32_t* cnt,
@@ -6213,8 +6206,8 @@ void scatter_partials(const uint64_t* keys, const uint64_t* acc, const uint32_t*
   const size_t lds = (size_t)nb * 2 * sizeof(uint32_t);
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)scatter_partials_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)scatter_partials_kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   const int64_t per = (int64_t)kScatThreads * kScatU;
@@ -6222,7 +6215,7 @@ void scatter_partials(const uint64_t* keys, const uint64_t* acc, const uint32_t*
   hipLaunchKernelGGL(scatter_partials_kernel, dim3(grid), dim3(kScatThreads), lds,
                      (hipStream_t)stream, keys, acc, cnt, n_in, plan, jhash, kg_dest, cursor, out,
                      flags);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void expr_filter(const double* x, int64_t n, const ExprProg& prog, uint8_t* keep,
@@ -6231,13 +6224,13 @@ void expr_filter(const double* x, int64_t n, const ExprProg& prog, uint8_t* keep
   const size_t lds = (size_t)(kExprVars + prog.depth) * 256 * sizeof(double);
   hipLaunchKernelGGL(expr_filter_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), lds,
                      (hipStream_t)stream, x, n, prog, keep);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void line_starts(const uint8_t* buf, int64_t n, void* scratch, int64_t* idx, int64_t* total,
                  intptr_t stream, int64_t cap) {
   if (n <= 0) {
-    HIP_CHECK(hipMemsetAsync(total, 0, 8, (hipStream_t)stream));
+    MXS_HIP_CHECK(hipMemsetAsync(total, 0, 8, (hipStream_t)stream));
     return;
   }
   const int64_t nt = (n + kFcTile - 1) / kFcTile;
@@ -6246,23 +6239,23 @@ void line_starts(const uint8_t* buf, int64_t n, void* scratch, int64_t* idx, int
   uint32_t* counts = (uint32_t*)(offs + nt);
   hipLaunchKernelGGL(line_start_mask_kernel, dim3((uint32_t)nt), dim3(256), 0,
                      (hipStream_t)stream, buf, n, masks, counts);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, nt,
                      offs, total);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(filter_write_kernel, dim3((uint32_t)nt), dim3(256), 0, (hipStream_t)stream,
                      masks, offs, n, idx, cap);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void compact_from_masks(const uint64_t* masks, const uint32_t* counts, int64_t nt, int64_t n,
                         int64_t* offs, int64_t* idx, int64_t* total, intptr_t stream) {
   hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, nt,
                      offs, total);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(filter_write_kernel, dim3((uint32_t)nt), dim3(256), 0, (hipStream_t)stream,
                      masks, offs, n, idx, INT64_MAX);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 int64_t filter_compact_scratch_bytes(int64_t n) {
@@ -6273,7 +6266,7 @@ int64_t filter_compact_scratch_bytes(int64_t n) {
 void expr_filter_compact(const double* x, int64_t n, const ExprProg& prog, void* scratch,
                          int64_t* idx, int64_t* total, intptr_t stream) {
   if (n <= 0) {
-    HIP_CHECK(hipMemsetAsync(total, 0, 8, (hipStream_t)stream));
+    MXS_HIP_CHECK(hipMemsetAsync(total, 0, 8, (hipStream_t)stream));
     return;
   }
   const int64_t nt = (n + kFcTile - 1) / kFcTile;
@@ -6283,13 +6276,13 @@ void expr_filter_compact(const double* x, int64_t n, const ExprProg& prog, void*
   const size_t lds = (size_t)(kExprVars + prog.depth) * 256 * sizeof(double);
   hipLaunchKernelGGL(filter_mask_kernel, dim3((uint32_t)nt), dim3(256), lds, (hipStream_t)stream,
                      x, n, prog, masks, counts);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, nt,
                      offs, total);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(filter_write_kernel, dim3((uint32_t)nt), dim3(256), 0, (hipStream_t)stream,
                      masks, offs, n, idx, INT64_MAX);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void rolling(const Rec*, const uint32_t*, const RollPlan&, uint64_t*, uint64_t*, uint32_t*,
@@ -6313,7 +6306,7 @@ void rolling_lookup(const Rec* recs, const uint32_t* counts, int nsrc, int nsub,
                      (hipStream_t)stream,
                      recs, counts, nsrc, nsub, bucket_cap, cap_log2, keys_g, sort_key, vals_out,
                      n_out, flags, abits, shift);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void rolling_lookup_direct(const uint64_t* keys, const uint64_t* vals, uint32_t n, int nsub_log2,
@@ -6325,14 +6318,14 @@ void rolling_lookup_direct(const uint64_t* keys, const uint64_t* vals, uint32_t 
   hipLaunchKernelGGL(rolling_lookup_direct_kernel, dim3(grid_for(n > 0 ? (n + 3) / 4 : 1, 256, 8192)),
                      dim3(256), 0, (hipStream_t)stream, keys, vals, n, nsub_log2, cap_log2, keys_g,
                      sort_key, vals_out, n_out, flags, shift);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void rolling_heads(const int64_t* sk, const uint32_t* n_in, int64_t n_cap, uint32_t* heads,
                    uint32_t* n_heads, int shift, intptr_t stream) {
   hipLaunchKernelGGL(seg_heads_kernel, dim3(grid_for((n_cap + 63) / 64, 256, 4096)), dim3(256), 0,
                      (hipStream_t)stream, sk, n_in, heads, n_heads, shift);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 template <int AGG>
@@ -6365,7 +6358,7 @@ void rolling_scan(int agg, const int64_t* sk, const int64_t* perm, const uint64_
 #undef MXS_R
     default: throw std::runtime_error("rolling_scan: unsupported aggregate");
   }
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void rolling_argscan(int agg, const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
@@ -6383,7 +6376,7 @@ void rolling_argscan(int agg, const int64_t* sk, const uint64_t* vals, const uin
 #undef MXS_R
     default: throw std::invalid_argument("rolling_argscan: min / max aggregates only");
   }
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void rolling_slide_scan(int agg, const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
@@ -6410,7 +6403,7 @@ void rolling_slide_scan(int agg, const int64_t* sk, const uint64_t* vals, const 
 #undef MXS_R
     default: throw std::runtime_error("rolling_slide_scan: unsupported aggregate");
   }
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 
@@ -6453,7 +6446,7 @@ void session_lookup(const void* recs, const uint32_t* counts, int nsrc, int nsub
                        spill_set, spill_mask, spill_any, sk, vals, n_out, host_recs, n_host,
                        host_cap, n_inserted, tbits);
   }
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 size_t session_lookup_sort_lds(int cap_log2, uint32_t m_cap) {
@@ -6484,8 +6477,8 @@ bool session_lookup_sort(const void* recs, const uint32_t* counts, int nsrc, int
   static bool attr[2] = {false, false};
   if (!attr[rec_words - 2]) {
     // dynamic + the kernel's static LDS (slot flags, segment offsets, scan scratch) <= 160 KiB
-    HIP_CHECK(hipFuncSetAttribute((const void*)kfn,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)kfn,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
     attr[rec_words - 2] = true;
   }
   hipLaunchKernelGGL(kfn, dim3(nsub), dim3(kSessSortBlock), lds,
@@ -6493,7 +6486,7 @@ bool session_lookup_sort(const void* recs, const uint32_t* counts, int nsrc, int
                      spill_set, spill_mask, spill_any, sort_out, vals_out, n_out, host_recs,
                      n_host, host_cap, n_inserted, tbits, m_cap, skip, skip_mask, heads_out,
                      n_heads, pair);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   return true;
 }
 
@@ -6501,7 +6494,7 @@ void session_heads(const int64_t* sk, const uint32_t* n_in, int64_t n_cap, uint3
                    uint32_t* n_heads, intptr_t stream) {
   hipLaunchKernelGGL(seg_heads_kernel, dim3(grid_for((n_cap + 63) / 64, 256, 4096)), dim3(256), 0,
                      (hipStream_t)stream, sk, n_in, heads, n_heads, 32);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_merge(const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
@@ -6516,11 +6509,11 @@ void session_merge(const int64_t* sk, const uint64_t* vals, const uint32_t* n_in
                   ovf_slots, n_ovf, ovf_rows, n_ovf_runs, ovf_cap};
   hipLaunchKernelGGL(session_merge_small_kernel, dim3(grid_for(n_cap, 256, 16384)), dim3(256), 0,
                      (hipStream_t)stream, sk, vals, n_in, a, o, long_heads, n_long);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   // Long segments (hot keys): a wave each; the count stays on the device (grid-stride waves).
   hipLaunchKernelGGL(session_merge_long_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, sk,
                      vals, n_in, long_heads, n_long, a, o);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_merge_heads(const int64_t* sk, const uint64_t* vals, const uint32_t* n_in,
@@ -6539,10 +6532,10 @@ void session_merge_heads(const int64_t* sk, const uint64_t* vals, const uint32_t
                   ovf_slots, n_ovf, ovf_rows, n_ovf_runs, ovf_cap};
   hipLaunchKernelGGL(session_merge_heads_kernel, dim3(grid_for(head_cap, 256, 16384)), dim3(256),
                      0, (hipStream_t)stream, sk, vals, heads, n_heads, a, o, long_heads, n_long);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(session_merge_long_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, sk,
                      vals, n_in, long_heads, n_long, a, o);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_fire(int64_t gap, int64_t lateness, int64_t wm, int agg, int cap_log2,
@@ -6557,7 +6550,7 @@ void session_fire(int64_t gap, int64_t lateness, int64_t wm, int agg, int cap_lo
                      (hipStream_t)stream, a, keys_g, reinterpret_cast<SessRec*>(sess),
                      slot_due, map, filt, out_key, out_start, out_end, out_val, out_raw, out_cnt,
                      out_n, out_cap);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_evict(int64_t nslots, int cap_log2, uint64_t* keys_g, int64_t* sess,
@@ -6575,7 +6568,7 @@ void session_evict(int64_t nslots, int cap_log2, uint64_t* keys_g, int64_t* sess
                      slot_due, slot_last, idle_before, slots, nslots_list, spill_set, spill_mask,
                      st_key, st_start, st_end, st_acc, st_cnt, st_flags, n_rows, row_cap,
                      n_evicted);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_rehash(int64_t nslots, int cap_log2, const uint64_t* keys_o, const int64_t* sess_o,
@@ -6585,7 +6578,7 @@ void session_rehash(int64_t nslots, int cap_log2, const uint64_t* keys_o, const 
   hipLaunchKernelGGL(session_rehash_kernel, dim3(grid_for(nslots, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, a, keys_o, reinterpret_cast<const SessRec*>(sess_o), due_o,
                      last_o, keys_n, reinterpret_cast<SessRec*>(sess_n), due_n, last_n, inserted);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void set_rehash(const uint64_t* old, int64_t n_old, uint64_t* neu, uint32_t new_mask,
@@ -6593,7 +6586,7 @@ void set_rehash(const uint64_t* old, int64_t n_old, uint64_t* neu, uint32_t new_
   if (n_old <= 0) return;
   hipLaunchKernelGGL(set_rehash_kernel, dim3(grid_for(n_old, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, old, n_old, neu, new_mask);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void set_insert_keys(uint64_t* set, uint32_t mask, const int64_t* keys, int64_t n,
@@ -6601,7 +6594,7 @@ void set_insert_keys(uint64_t* set, uint32_t mask, const int64_t* keys, int64_t 
   if (n <= 0) return;
   hipLaunchKernelGGL(set_insert_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0,
                      (hipStream_t)stream, set, mask, keys, n);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void set_probe(const uint64_t* set, uint32_t mask, const int64_t* keys, int64_t n, uint8_t* hit,
@@ -6609,14 +6602,14 @@ void set_probe(const uint64_t* set, uint32_t mask, const int64_t* keys, int64_t 
   if (n <= 0) return;
   hipLaunchKernelGGL(set_probe_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0,
                      (hipStream_t)stream, set, mask, keys, n, hit, n_hit);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void set_erase(uint64_t* set, uint32_t mask, const int64_t* keys, int64_t n, intptr_t stream) {
   if (n <= 0) return;
   hipLaunchKernelGGL(set_erase_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0,
                      (hipStream_t)stream, set, mask, keys, n);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void keygroups(const uint64_t* keys, int64_t n, int hash_mode, const int32_t* jhash, int max_par,
@@ -6624,7 +6617,7 @@ void keygroups(const uint64_t* keys, int64_t n, int hash_mode, const int32_t* jh
   if (n <= 0) return;
   hipLaunchKernelGGL(keygroup_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, keys, n, hash_mode, jhash, max_par, kg);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void table_insert(const uint64_t* keys, int64_t n, int nsub_log2, int cap_log2, uint64_t* keys_g,
@@ -6632,7 +6625,7 @@ void table_insert(const uint64_t* keys, int64_t n, int nsub_log2, int cap_log2, 
   if (n <= 0) return;
   hipLaunchKernelGGL(table_insert_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, keys, n, nsub_log2, cap_log2, keys_g, slots);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_promote(const int64_t* slots, const int64_t* rec, const int64_t* last, int64_t n,
@@ -6641,7 +6634,7 @@ void session_promote(const int64_t* slots, const int64_t* rec, const int64_t* la
   if (n <= 0) return;
   hipLaunchKernelGGL(session_promote_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0,
                      (hipStream_t)stream, slots, rec, last, n, sess, slot_due, slot_last, n_bad);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_promote_rows(const int64_t* rows, int64_t n, int nsub_log2, int cap_log2,
@@ -6653,7 +6646,7 @@ void session_promote_rows(const int64_t* rows, int64_t n, int nsub_log2, int cap
     hipLaunchKernelGGL(session_promote_rows_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0,
                        (hipStream_t)stream, rows, n, nsub_log2, cap_log2, phase, keys_g, slots,
                        sess, slot_due, slot_last, inserted, n_bad);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void session_slot_insert(const uint64_t* keys, int64_t n, int nsub_log2, int cap_log2,
@@ -6661,7 +6654,7 @@ void session_slot_insert(const uint64_t* keys, int64_t n, int nsub_log2, int cap
   if (n <= 0) return;
   hipLaunchKernelGGL(session_slot_insert_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, keys, n, nsub_log2, cap_log2, keys_g, slots, inserted);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 template <int AGG>
@@ -6675,10 +6668,10 @@ static void launch_combine(const Rec* recs, const uint32_t* counts, int nbuckets
     if (p.rec_words <= 2 && agg_pack_ok(q)) {
       static bool attr_pk = false;
       if (!attr_pk) {
-        HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 1, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 2, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 1, true>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 2, true>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_pk = true;
       }
       const size_t cap = (size_t)1 << p.cap_log2;
@@ -6694,12 +6687,12 @@ static void launch_combine(const Rec* recs, const uint32_t* counts, int nbuckets
   }
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 3>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 2>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 1>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 3>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 2>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)window_combine_kernel<AGG, 1>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   if (p.rec_words == 1)
@@ -6728,14 +6721,14 @@ void window_combine(const Rec* recs, const uint32_t* counts, int nbuckets, const
 #undef MXS_C
     default: throw std::runtime_error("window_combine: unsupported aggregate");
   }
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void f64_order_bits(const uint64_t* v, int64_t n, uint64_t* o, intptr_t stream) {
   if (n <= 0) return;
   hipLaunchKernelGGL(f64_order_bits_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, v, n, o);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
@@ -6743,7 +6736,7 @@ void segment_median_select(const int64_t* heads, int64_t nseg, int64_t total, co
   if (nseg <= 0) return;
   hipLaunchKernelGGL(segment_median_select_kernel, dim3(grid_for(nseg, 4, 16384)), dim3(256), 0,
                      (hipStream_t)stream, heads, nseg, total, ord, out);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
@@ -6756,7 +6749,7 @@ void segment_quantile_select(const int64_t* heads, int64_t nseg, int64_t total,
   if (nseg <= 0) return;
   hipLaunchKernelGGL(segment_quantile_select_kernel, dim3(grid_for(nseg, 4, 16384)), dim3(256), 0,
                      (hipStream_t)stream, heads, nseg, total, ord, qs, out);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void topn_select(const TopnCols& in, const uint32_t* bounds, const TopnPlan& p,
@@ -6768,18 +6761,18 @@ void topn_select(const TopnCols& in, const uint32_t* bounds, const TopnPlan& p,
   const uint32_t rank0 = (uint32_t)std::min<int64_t>(p.n - 1, 0xFFFFFFFFll);
   hipLaunchKernelGGL(topn_init_kernel, dim3(grid_for((int64_t)p.nwin * kTopnStateWords, 256, 1024)),
                      dim3(256), 0, s, state, p.nwin, rank0);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
   // ~1024 workgroups over the batch (4 per CU), each window's rows in grid-stride tiles.
   const dim3 grid(grid_for(p.cap, kTopnBlock * 4, std::max(1, 1024 / p.nwin)), p.nwin);
   for (int pass = 0; pass < 8; ++pass) {
     hipLaunchKernelGGL(topn_hist_kernel, grid, dim3(kTopnBlock), 0, s, in, bounds, p, state, pass);
-    HIP_CHECK(hipGetLastError());
+    MXS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(topn_pick_kernel, dim3(p.nwin), dim3(64), 0, s, bounds, p, state, pass);
-    HIP_CHECK(hipGetLastError());
+    MXS_HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(topn_compact_kernel, grid, dim3(kTopnBlock), 0, s, in, bounds, p, state, out,
                      out_bounds);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void segment_median(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
@@ -6787,7 +6780,7 @@ void segment_median(const int64_t* heads, int64_t nseg, int64_t total, const uin
   if (nseg <= 0) return;
   hipLaunchKernelGGL(segment_median_kernel, dim3(grid_for(nseg, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, heads, nseg, total, ord, out);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void tier_merge(const uint64_t* keys, const uint64_t* acc, const uint32_t* cnt, int64_t n,
@@ -6797,7 +6790,7 @@ void tier_merge(const uint64_t* keys, const uint64_t* acc, const uint32_t* cnt, 
   hipLaunchKernelGGL(tier_merge_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, keys, acc, cnt, n, n_dev, mode, agg, tkeys, tacc, tcnt,
                      tdirty, mask, flags);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

@@ -14,24 +14,12 @@
 #include <stdexcept>
 #include <string>
 
+#include "mxs_hip_util.h"
 #include "mxs_listwin.h"
+#include "pair_scan.h"
 
 namespace mxs {
 namespace {
-
-#define LW_CHECK(x)                                                                         \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
-int grid_of(int64_t n, int per_block, int cap) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < cap ? g : cap);
-}
 
 __device__ __forceinline__ int lw_slot(int64_t t, int64_t offset, int64_t pane, int ring,
                                        int64_t late_ts) {
@@ -158,136 +146,27 @@ __global__ __launch_bounds__(kLwBlock) void lw_rank_scatter_kernel(LwRankPanes w
   }
 }
 
-// ---- order-preserving scan of the key counts ---------------------------------------------
-// Block-wide exclusive scan of one value per thread (1024 threads): wave shuffles + wave totals.
-template <class T>
-__device__ __forceinline__ T block_excl_scan(T v, T* wsum, T* total) {
-  T incl = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(incl, d);
-    if ((int)(threadIdx.x & 63) >= d) incl += y;
-  }
-  const int wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 63) wsum[wv] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    T t = 0;
-    for (int i = 0; i < nw; ++i) {
-      const T c = wsum[i];
-      wsum[i] = t;
-      t += c;
-    }
-    *total = t;
-  }
-  __syncthreads();
-  const T r = wsum[wv] + incl - v;
-  __syncthreads();
-  return r;
-}
+// ---- order-preserving scan of the key counts (csrc/pair_scan.h, plain 64-bit sums) ----------
+static_assert(kLwScanTile == kJoinScanTile, "lw_scan_scratch_bytes is sized by the pair scan");
 
-constexpr int kScanThreads = 1024;
-constexpr int kScanPer = kLwScanTile / kScanThreads;  // 4 keys per thread
+struct LwScan {
+  using Add = Add64;
+  const uint32_t* counts;
+  int64_t nkeys, kmin;
+  int64_t *offs, *heads, *head_keys, *nheads;
 
-// Pass 1: per tile, the element total and the number of non-empty keys.
-__global__ __launch_bounds__(kScanThreads) void lw_tile_sums_kernel(
-    const uint32_t* __restrict__ counts, int64_t nkeys, uint64_t* __restrict__ tsum,
-    uint32_t* __restrict__ tne) {
-  __shared__ uint64_t ws[16];
-  __shared__ uint32_t wn[16];
-  __shared__ uint64_t tot;
-  __shared__ uint32_t totn;
-  const int64_t k0 = (int64_t)blockIdx.x * kLwScanTile + (int64_t)threadIdx.x * kScanPer;
-  uint64_t s = 0;
-  uint32_t ne = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    const uint32_t c = k0 + j < nkeys ? counts[k0 + j] : 0u;
-    s += c;
-    ne += c ? 1u : 0u;
+  __device__ __forceinline__ uint64_t count(int64_t i) const { return counts[i]; }
+  __device__ __forceinline__ void element(int64_t i, uint64_t o) const { offs[i] = (int64_t)o; }
+  // the (start, key) of a non-empty key, in key order
+  __device__ __forceinline__ void nonempty(int64_t i, int64_t h, uint64_t o) const {
+    heads[h] = (int64_t)o;
+    head_keys[h] = kmin + i;
   }
-  block_excl_scan<uint64_t>(s, ws, &tot);
-  block_excl_scan<uint32_t>(ne, wn, &totn);
-  if (threadIdx.x == 0) {
-    tsum[blockIdx.x] = tot;
-    tne[blockIdx.x] = totn;
+  __device__ __forceinline__ void finish(uint64_t total, uint32_t m) const {
+    offs[nkeys] = (int64_t)total;
+    *nheads = (int64_t)m;
   }
-}
-
-// Pass 2 (one workgroup): exclusive scan of the tile totals (<= kScanThreads * 4 tiles).
-__global__ __launch_bounds__(kScanThreads) void lw_tile_scan_kernel(uint64_t* __restrict__ tsum,
-                                                                    uint32_t* __restrict__ tne,
-                                                                    int64_t ntiles,
-                                                                    int64_t* __restrict__ offs_end,
-                                                                    int64_t nkeys,
-                                                                    int64_t* __restrict__ nheads) {
-  __shared__ uint64_t ws[16];
-  __shared__ uint32_t wn[16];
-  __shared__ uint64_t tot;
-  __shared__ uint32_t totn;
-  const int64_t t0 = (int64_t)threadIdx.x * 4;
-  uint64_t s[4];
-  uint32_t e[4];
-  uint64_t ss = 0;
-  uint32_t se = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    s[j] = t0 + j < ntiles ? tsum[t0 + j] : 0ull;
-    e[j] = t0 + j < ntiles ? tne[t0 + j] : 0u;
-    ss += s[j];
-    se += e[j];
-  }
-  uint64_t bs = block_excl_scan<uint64_t>(ss, ws, &tot);
-  uint32_t be = block_excl_scan<uint32_t>(se, wn, &totn);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (t0 + j < ntiles) {
-      tsum[t0 + j] = bs;
-      tne[t0 + j] = be;
-    }
-    bs += s[j];
-    be += e[j];
-  }
-  if (threadIdx.x == 0) {
-    offs_end[nkeys] = (int64_t)tot;
-    *nheads = (int64_t)totn;
-  }
-}
-
-// Pass 3: per tile, exclusive offsets of every key and the (start, key) of non-empty keys in
-// key order.
-__global__ __launch_bounds__(kScanThreads) void lw_tile_write_kernel(
-    const uint32_t* __restrict__ counts, int64_t nkeys, int64_t kmin,
-    const uint64_t* __restrict__ tsum, const uint32_t* __restrict__ tne, int64_t* __restrict__ offs,
-    int64_t* __restrict__ heads, int64_t* __restrict__ head_keys) {
-  __shared__ uint64_t ws[16];
-  __shared__ uint32_t wn[16];
-  __shared__ uint64_t tot;
-  __shared__ uint32_t totn;
-  const int64_t k0 = (int64_t)blockIdx.x * kLwScanTile + (int64_t)threadIdx.x * kScanPer;
-  uint32_t c[kScanPer];
-  uint64_t s = 0;
-  uint32_t ne = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    c[j] = k0 + j < nkeys ? counts[k0 + j] : 0u;
-    s += c[j];
-    ne += c[j] ? 1u : 0u;
-  }
-  uint64_t o = tsum[blockIdx.x] + block_excl_scan<uint64_t>(s, ws, &tot);
-  uint32_t h = tne[blockIdx.x] + block_excl_scan<uint32_t>(ne, wn, &totn);
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    if (k0 + j < nkeys) {
-      offs[k0 + j] = (int64_t)o;
-      if (c[j]) {
-        heads[h] = (int64_t)o;
-        head_keys[h] = kmin + k0 + j;
-        ++h;
-      }
-    }
-    o += c[j];
-  }
-}
+};
 
 // ---- distinct count of every segment (func "distinct") -------------------------------------
 // The slot of word x in a table of `cap` (power of two) slots is the top log2(cap) bits of
@@ -472,7 +351,7 @@ void lw_pane_count(const int64_t* ts, int64_t n, int64_t offset, int64_t pane, i
   const size_t lds = sizeof(uint32_t) * (size_t)(ring + 1);
   hipLaunchKernelGGL(lw_pane_count_kernel, dim3(grid_of(n, kLwBlock * 16, 2048)), dim3(kLwBlock),
                      lds, (hipStream_t)stream, ts, n, offset, pane, ring, late_ts, counts);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void lw_pane_scatter(const int64_t* keys, const int64_t* ts, const uint64_t* vals, int64_t n,
@@ -485,7 +364,7 @@ void lw_pane_scatter(const int64_t* keys, const int64_t* ts, const uint64_t* val
   hipLaunchKernelGGL(lw_pane_scatter_kernel, dim3(grid_of(n, kLwBlock * kLwItems, 4096)),
                      dim3(kLwBlock), lds, (hipStream_t)stream, keys, ts, vals, n, offset, pane,
                      ring, late_ts, tab, cursor);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void lw_key_count(const LwPanes& w, int64_t kmin, int64_t nkeys, uint32_t* counts,
@@ -497,30 +376,18 @@ void lw_key_count(const LwPanes& w, int64_t kmin, int64_t nkeys, uint32_t* count
   if (mx <= 0) return;
   hipLaunchKernelGGL(lw_key_count_kernel, dim3(grid_of(mx, kLwBlock * 8, 4096), w.n),
                      dim3(kLwBlock), 0, (hipStream_t)stream, w, kmin, counts);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
-int64_t lw_scan_scratch_bytes(int64_t nkeys) {
-  const int64_t nt = (nkeys + kLwScanTile - 1) / kLwScanTile;
-  return nt * (int64_t)(sizeof(uint64_t) + sizeof(uint32_t)) + 64;
-}
+int64_t lw_scan_scratch_bytes(int64_t nkeys) { return pair_scan_scratch_bytes(nkeys); }
 
 void lw_scan(const uint32_t* counts, int64_t nkeys, int64_t kmin, void* scratch, int64_t* offs,
              int64_t* heads, int64_t* head_keys, int64_t* nheads, intptr_t stream) {
   if (nkeys <= 0) throw std::invalid_argument("lw_scan: empty key range");
-  const int64_t nt = (nkeys + kLwScanTile - 1) / kLwScanTile;
-  if (nt > (int64_t)kScanThreads * 4)
+  if (nkeys > (16ll << 20))  // the callers' key ranges are far below; kept as their contract
     throw std::invalid_argument("lw_scan: more than 16 Mi keys");
-  uint64_t* tsum = reinterpret_cast<uint64_t*>(scratch);
-  uint32_t* tne = reinterpret_cast<uint32_t*>(tsum + nt);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(lw_tile_sums_kernel, dim3(nt), dim3(kScanThreads), 0, s, counts, nkeys, tsum,
-                     tne);
-  hipLaunchKernelGGL(lw_tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, tsum, tne, nt, offs,
-                     nkeys, nheads);
-  hipLaunchKernelGGL(lw_tile_write_kernel, dim3(nt), dim3(kScanThreads), 0, s, counts, nkeys,
-                     kmin, tsum, tne, offs, heads, head_keys);
-  LW_CHECK(hipGetLastError());
+  const LwScan p = {counts, nkeys, kmin, offs, heads, head_keys, nheads};
+  pair_scan_launch(p, nkeys, scratch, (hipStream_t)stream);
 }
 
 void lw_key_scatter(const LwPanes& w, int64_t kmin, int64_t* cursor, uint64_t* out_ord,
@@ -531,7 +398,7 @@ void lw_key_scatter(const LwPanes& w, int64_t kmin, int64_t* cursor, uint64_t* o
   if (mx <= 0) return;
   hipLaunchKernelGGL(lw_key_scatter_kernel, dim3(grid_of(mx, kLwBlock * 8, 4096), w.n),
                      dim3(kLwBlock), 0, (hipStream_t)stream, w, kmin, cursor, out_ord);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void lw_rank_prefix(const LwRankPanes& w, int64_t kmin, int64_t nkeys, uint32_t* total,
@@ -540,7 +407,7 @@ void lw_rank_prefix(const LwRankPanes& w, int64_t kmin, int64_t nkeys, uint32_t*
   if (nkeys <= 0) return;
   hipLaunchKernelGGL(lw_rank_prefix_kernel, dim3(grid_of(nkeys, kLwBlock, 4096)), dim3(kLwBlock),
                      0, (hipStream_t)stream, w, kmin, nkeys, total, pre);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void lw_rank_scatter(const LwRankPanes& w, int64_t kmin, int64_t nkeys, const int64_t* offs,
@@ -551,7 +418,7 @@ void lw_rank_scatter(const LwRankPanes& w, int64_t kmin, int64_t nkeys, const in
   if (mx <= 0) return;
   hipLaunchKernelGGL(lw_rank_scatter_kernel, dim3(grid_of(mx, kLwBlock * 8, 4096), w.n),
                      dim3(kLwBlock), 0, (hipStream_t)stream, w, kmin, nkeys, offs, pre, out_ord);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void segment_distinct_short(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
@@ -564,7 +431,7 @@ void segment_distinct_short(const int64_t* heads, int64_t nseg, int64_t total, c
   if (nseg <= 0) return;
   hipLaunchKernelGGL(segment_distinct_short_kernel, dim3(grid_of(nseg, 4, 16384)), dim3(256), 0,
                      (hipStream_t)stream, heads, nseg, total, ord, out, list, list_cap, meta);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void segment_distinct_long(const int64_t* heads, int64_t nseg, int64_t total, const uint64_t* ord,
@@ -576,7 +443,7 @@ void segment_distinct_long(const int64_t* heads, int64_t nseg, int64_t total, co
   hipLaunchKernelGGL(segment_distinct_long_kernel, dim3(grid_of(long_elems, kDistinctTile, 8192)),
                      dim3(256), 0, (hipStream_t)stream, heads, nseg, total, ord, list, n_long,
                      long_elems, scratch, out, meta);
-  LW_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

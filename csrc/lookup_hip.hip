@@ -12,21 +12,12 @@
 #include <stdexcept>
 #include <string>
 
+#include "mxs_hip_util.h"
 #include "mxs_lookup.h"
 #include "mxs_blockscan.h"
 
 namespace mxs {
 namespace {
-
-#define LOOKUP_CHECK(x)                                                                     \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
-typedef long long ll2 __attribute__((ext_vector_type(2)));
 
 constexpr int kLookupBlock = 256;
 constexpr int kLookupWaves = kLookupBlock / 64;
@@ -34,16 +25,6 @@ constexpr int kLookupRounds = kLookupTile / kLookupBlock;  // rows per lane of a
 constexpr int kLookupBatch = 8;            // rounds whose loads are in flight together
 constexpr int kLookupMaxGrid = 1 << 20;    // longer inputs stride over their tiles
 constexpr int kScanThreads = 1024;
-
-int grid_of(int64_t n, int per_block, int cap) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < cap ? g : cap);
-}
-
-struct Add64 {
-  __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
 
 // The value in force for key k (one 16-byte load when k is inside the table).
 template <bool kHasDefault>
@@ -248,7 +229,7 @@ void lookup_upsert(const int64_t* skeys, const int64_t* perm, const int64_t* val
   hipLaunchKernelGGL(lookup_upsert_kernel, dim3(grid_of(n, 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, skeys, perm, vals, n, reinterpret_cast<ll2*>(table),
                      cap);
-  LOOKUP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void lookup_mask(const int64_t* keys, const int64_t* vals, int64_t n, const int64_t* table,
@@ -277,7 +258,7 @@ void lookup_mask(const int64_t* keys, const int64_t* vals, int64_t n, const int6
     LOOKUP_MASK_CASE(kLookupNe);
   }
 #undef LOOKUP_MASK_CASE
-  LOOKUP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void lookup_scan(const uint32_t* counts, int64_t ntiles, int64_t* offsets, int64_t* meta,
@@ -285,7 +266,7 @@ void lookup_scan(const uint32_t* counts, int64_t ntiles, int64_t* offsets, int64
   if (ntiles < 0) throw std::invalid_argument("lookup_scan: negative tile count");
   hipLaunchKernelGGL(lookup_scan_kernel, dim3(1), dim3(kScanThreads), 0, (hipStream_t)stream,
                      counts, ntiles, offsets, meta);
-  LOOKUP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 // `words`, `counts` and `offsets` must be lookup_mask's and lookup_scan's output for these same
@@ -310,7 +291,7 @@ void lookup_emit(const int64_t* keys, const int64_t* vals, const int64_t* ts, in
     hipLaunchKernelGGL(lookup_emit_kernel<false>, grid, dim3(kLookupBlock), 0, s, keys, vals, ts,
                        n, t, cap, default_bits, ntiles, words, counts, offsets, kept, out_key,
                        out_val, out_t, out_ts);
-  LOOKUP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void lookup_gather(const int64_t* keys, const int64_t* vals, const int64_t* ts, int64_t n,
@@ -322,7 +303,7 @@ void lookup_gather(const int64_t* keys, const int64_t* vals, const int64_t* ts, 
   hipLaunchKernelGGL(lookup_gather_kernel, dim3(grid_of(n, 256, 16384)), dim3(256), 0,
                      (hipStream_t)stream, keys, vals, ts, n, reinterpret_cast<const ll2*>(table),
                      cap, default_bits, out_key, out_val, out_t, out_ts);
-  LOOKUP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

@@ -1,22 +1,18 @@
-// mxstream — the block-wide exclusive scan and the two scan operators that the pair scans of the
-// window join (csrc/join_hip.hip) and of the interval join (csrc/ijoin_hip.hip) share.
-// Device code only: include from a .hip file after mxs_join.h.
+// mxstream — the block-wide exclusive scan and the plain add operators for every unit that scans
+// inside a workgroup (csrc/pair_scan.h, csrc/lookup_hip.hip). Device code only: include from a
+// .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "mxs_join.h"
-
 namespace mxs {
 
-struct SatAdd {
-  __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const {
-    return join_sat_add(a, b);
-  }
-};
 struct Add32 {
   __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
+};
+struct Add64 {
+  __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
 };
 
 // Block-wide exclusive scan of one value per thread (up to 1024 threads) under an associative

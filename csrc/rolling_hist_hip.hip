@@ -33,18 +33,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "mxs_hip_util.h"
 #include "mxs_kernels.h"
 
 namespace mxs {
 namespace {
-
-#define HIP_CHECK(x)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
 
 constexpr int kHistThreads = 1024;
 constexpr int kTileWaves = 8;
@@ -643,10 +636,10 @@ void rolling_hist(const uint64_t* keys, int64_t n, int nsub_log2, int cap_log2, 
   }();
   static bool attr = false;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)rolling_hist_count_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIP_CHECK(hipFuncSetAttribute((const void*)rolling_hist_emit_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)rolling_hist_count_kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)rolling_hist_emit_kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   const uint32_t ns = (uint32_t)nslots;
@@ -661,7 +654,7 @@ void rolling_hist(const uint64_t* keys, int64_t n, int nsub_log2, int cap_log2, 
   hipLaunchKernelGGL(rolling_hist_emit_kernel, dim3(g.nb), dim3(kTile), lds, s, slot16,
                      (uint32_t)n, g.chunk, part, ns, keys_g, cnt_g, filt, need_key, dense, out_key,
                      out_val, out_tag, out_n, out_cap, ablate);
-  HIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

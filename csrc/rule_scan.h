@@ -1,8 +1,8 @@
-// mxstream — what the keyed rules' device code shares: the HIP error check, the 16-byte row type
-// and the grid size for their four units (csrc/timeout_hip.hip, sustain_hip.hip, burst_hip.hip,
-// reorder_hip.hip), and for the rules that scan a batch sorted by key
-// (sustain_scan_kernel, burst_scan_kernel) the scan frame: who owns a key's run, the append of a
-// transition, and when a wave walks on. Included from .hip files only.
+// mxstream — what the keyed rules' device code shares: the host helpers of csrc/mxs_hip_util.h
+// for their four units (csrc/timeout_hip.hip, sustain_hip.hip, burst_hip.hip, reorder_hip.hip),
+// and for the rules that scan a batch sorted by key (sustain_scan_kernel, burst_scan_kernel) the
+// scan frame: who owns a key's run, the append of a transition, and when a wave walks on.
+// Included from .hip files only.
 //
 // The frame. The batch arrives stably sorted by key (`skeys`, with `perm` = the arrival index of
 // every sorted row). A wave owns the key runs that BEGIN in its 64 sorted rows, its chunk: their
@@ -36,27 +36,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <stdexcept>
-#include <string>
+
+#include "mxs_hip_util.h"
 
 namespace mxs {
-
-#define MXS_HIP_CHECK(x)                                                                    \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
-
-typedef long long ll2 __attribute__((ext_vector_type(2)));
-
-// Workgroups for n items at `per_block` each: at least 1, at most `cap` (the kernels stride).
-inline int grid_of(int64_t n, int per_block, int cap) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < cap ? g : cap);
-}
 
 // A lane's place in the frame: sorted row i = b0 + lane, its key and arrival index.
 struct RuleFrame {

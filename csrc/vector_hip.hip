@@ -33,18 +33,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "mxs_hip_util.h"
 #include "mxs_vector.h"
 
 namespace mxs {
 namespace {
-
-#define VHIP_CHECK(x)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (x);                                                                    \
-    if (e_ != hipSuccess)                                                                   \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + \
-                               __FILE__ + ":" + std::to_string(__LINE__));                  \
-  } while (0)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -573,8 +566,8 @@ void launch_vagg(const void* recs, const uint32_t* counts, const VecAggPlan& p, 
                  uint32_t* occ, uint32_t* flags, size_t lds, hipStream_t s) {
   static bool attr = false;
   if (!attr) {
-    VHIP_CHECK(hipFuncSetAttribute((const void*)vec_window_agg_kernel<MODE, RW>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MXS_HIP_CHECK(hipFuncSetAttribute((const void*)vec_window_agg_kernel<MODE, RW>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
   hipLaunchKernelGGL((vec_window_agg_kernel<MODE, RW>), dim3(p.nsub), dim3(kVThreads), lds, s,
@@ -605,7 +598,7 @@ void vec_window_agg(const void* recs, const uint32_t* counts, const VecAggPlan& 
     case 3: launch_vagg<1, 3>(recs, counts, p, vec, keys_g, acc_g, cnt_g, dirty_g, occupancy, flags, lds, s); break;
     default: throw std::invalid_argument("vec_window_agg: mode must be 0 (MFMA) or 1 (VALU)");
   }
-  VHIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void vec_window_fire(const uint64_t* keys_g, const float* acc_g, const uint32_t* cnt_g,
@@ -615,7 +608,7 @@ void vec_window_fire(const uint64_t* keys_g, const float* acc_g, const uint32_t*
   hipLaunchKernelGGL(vec_window_fire_kernel, dim3(vgrid(p.nslots, kVFIter, 2048)),
                      dim3(kVFThreads), 0, (hipStream_t)stream, keys_g, acc_g, cnt_g, dirty_g, p,
                      out_keys, out_vec, out_cnt, out_n);
-  VHIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void gen_vectors(float* vec, int64_t n, int dim, uint64_t seed, uint64_t stream_id, uint64_t idx0,
@@ -623,7 +616,7 @@ void gen_vectors(float* vec, int64_t n, int dim, uint64_t seed, uint64_t stream_
   if (n <= 0) return;
   hipLaunchKernelGGL(gen_vectors_kernel, dim3(vgrid(n * (dim / 4), 256, 8192)), dim3(256), 0,
                      (hipStream_t)stream, vec, n, dim, seed, stream_id, idx0, lo, span);
-  VHIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 void vec_gather(const void* recs, int rec_words, const uint32_t* counts, int nb, uint32_t bcap,
@@ -632,7 +625,7 @@ void vec_gather(const void* recs, int rec_words, const uint32_t* counts, int nb,
   if (total <= 0) return;
   hipLaunchKernelGGL(vec_gather_kernel, dim3(vgrid(total, 8, 8192)), dim3(256), 0,
                      (hipStream_t)stream, recs, rec_words, counts, nb, bcap, vec, dim, out);
-  VHIP_CHECK(hipGetLastError());
+  MXS_HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace gpu

@@ -119,37 +119,29 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
     return out
 
 
-SANITIZE_SOURCES = ["kernels_cpu.cpp", "vector_cpu.cpp", "join_cpu.cpp", "tests/sanitize_main.cpp"]
+# The stand-alone ASan/UBSan programs, host code only (GPU sanitizers are not
+# available on the target pool): the C++ twins of a family + its csrc/tests/sanitize_*_main.cpp.
+# "" is the first harness, build/sanitize/mxs_sanitize; the others are mxs_sanitize_<name>.
+SANITIZE_PROGRAMS = {
+    "": ["kernels_cpu.cpp", "vector_cpu.cpp", "join_cpu.cpp", "tests/sanitize_main.cpp"],
+    "ijoin": ["ijoin_cpu.cpp", "tests/sanitize_ijoin_main.cpp"],
+    "lookup": ["lookup_cpu.cpp", "tests/sanitize_lookup_main.cpp"],
+    "timeout": ["timeout_cpu.cpp", "tests/sanitize_timeout_main.cpp"],
+    "sustain": ["sustain_cpu.cpp", "tests/sanitize_sustain_main.cpp"],
+    "burst": ["burst_cpu.cpp", "tests/sanitize_burst_main.cpp"],
+    "reorder": ["reorder_cpu.cpp", "tests/sanitize_reorder_main.cpp"],
+}
 SANITIZE_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                   "-fno-sanitize-recover=all"]
 
 
-def build_sanitize(verbose: bool = False) -> Path:
-    """Host sanitizer harness: the C++ twins + csrc/tests/sanitize_main.cpp
-    under AddressSanitizer + UndefinedBehaviorSanitizer (host code only; GPU sanitizers are not
-    available on the target pool). Returns the executable's path."""
+def build_sanitize_program(name: str = "", verbose: bool = False) -> Path:
+    """Build one program of SANITIZE_PROGRAMS under AddressSanitizer + UndefinedBehaviorSanitizer
+    (rebuilt when a source or a header is newer). Returns the executable's path."""
     out_dir = ROOT / "build" / "sanitize"
     out_dir.mkdir(parents=True, exist_ok=True)
-    exe = out_dir / "mxs_sanitize"
-    srcs = [CSRC / s for s in SANITIZE_SOURCES]
-    cmd = ["g++", "-std=c++17", *SANITIZE_FLAGS, f"-I{CSRC}", "-I/opt/rocm/include",
-           "-D__HIP_PLATFORM_AMD__", *[str(s) for s in srcs], "-o", str(exe)]
-    newest = max(s.stat().st_mtime for s in srcs + sorted(CSRC.glob("*.h")))
-    if not exe.exists() or exe.stat().st_mtime < newest:
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            raise RuntimeError(f"sanitize build failed: {' '.join(cmd)}\n{res.stderr}")
-        if verbose:
-            print(f"[mxstream.build] built {exe}")
-    return exe
-
-
-def _build_sanitize_program(name: str, sources: list[str], verbose: bool) -> Path:
-    """One stand-alone ASan/UBSan program build/sanitize/<name> from csrc sources."""
-    out_dir = ROOT / "build" / "sanitize"
-    out_dir.mkdir(parents=True, exist_ok=True)
-    exe = out_dir / name
-    srcs = [CSRC / s for s in sources]
+    exe = out_dir / ("mxs_sanitize_" + name if name else "mxs_sanitize")
+    srcs = [CSRC / s for s in SANITIZE_PROGRAMS[name]]
     cmd = ["g++", "-std=c++17", *SANITIZE_FLAGS, f"-I{CSRC}", "-I/opt/rocm/include",
            "-D__HIP_PLATFORM_AMD__", *[str(s) for s in srcs], "-o", str(exe)]
     hdrs = sorted(CSRC.glob("*.h")) + sorted((CSRC / "tests").glob("*.h"))
@@ -163,59 +155,14 @@ def _build_sanitize_program(name: str, sources: list[str], verbose: bool) -> Pat
     return exe
 
 
-SANITIZE_IJOIN_SOURCES = ["ijoin_cpu.cpp", "tests/sanitize_ijoin_main.cpp"]
+def build_sanitize(verbose: bool = False) -> Path:
+    return build_sanitize_program("", verbose)
 
 
-def build_sanitize_ijoin(verbose: bool = False) -> Path:
-    """The interval-join twins (csrc/ijoin_cpu.cpp) + csrc/tests/sanitize_ijoin_main.cpp under
-    AddressSanitizer + UndefinedBehaviorSanitizer: a stand-alone program of its own. Returns the
-    executable's path."""
-    return _build_sanitize_program("mxs_sanitize_ijoin", SANITIZE_IJOIN_SOURCES, verbose)
-
-
-SANITIZE_LOOKUP_SOURCES = ["lookup_cpu.cpp", "tests/sanitize_lookup_main.cpp"]
-
-
-def build_sanitize_lookup(verbose: bool = False) -> Path:
-    """The latest-value lookup twins (csrc/lookup_cpu.cpp) + csrc/tests/sanitize_lookup_main.cpp,
-    built the same way. Returns the executable's path."""
-    return _build_sanitize_program("mxs_sanitize_lookup", SANITIZE_LOOKUP_SOURCES, verbose)
-
-
-SANITIZE_TIMEOUT_SOURCES = ["timeout_cpu.cpp", "tests/sanitize_timeout_main.cpp"]
-
-
-def build_sanitize_timeout(verbose: bool = False) -> Path:
-    """The keyed timer twins (csrc/timeout_cpu.cpp) + csrc/tests/sanitize_timeout_main.cpp,
-    built the same way. Returns the executable's path."""
-    return _build_sanitize_program("mxs_sanitize_timeout", SANITIZE_TIMEOUT_SOURCES, verbose)
-
-
-SANITIZE_SUSTAIN_SOURCES = ["sustain_cpu.cpp", "tests/sanitize_sustain_main.cpp"]
-
-
-def build_sanitize_sustain(verbose: bool = False) -> Path:
-    """The sustained-alert twin (csrc/sustain_cpu.cpp) + csrc/tests/sanitize_sustain_main.cpp,
-    built the same way. Returns the executable's path."""
-    return _build_sanitize_program("mxs_sanitize_sustain", SANITIZE_SUSTAIN_SOURCES, verbose)
-
-
-SANITIZE_BURST_SOURCES = ["burst_cpu.cpp", "tests/sanitize_burst_main.cpp"]
-
-
-def build_sanitize_burst(verbose: bool = False) -> Path:
-    """The burst-alert twin (csrc/burst_cpu.cpp) + csrc/tests/sanitize_burst_main.cpp, built the
-    same way. Returns the executable's path."""
-    return _build_sanitize_program("mxs_sanitize_burst", SANITIZE_BURST_SOURCES, verbose)
-
-
-SANITIZE_REORDER_SOURCES = ["reorder_cpu.cpp", "tests/sanitize_reorder_main.cpp"]
-
-
-def build_sanitize_reorder(verbose: bool = False) -> Path:
-    """The reorder-buffer twins (csrc/reorder_cpu.cpp) + csrc/tests/sanitize_reorder_main.cpp,
-    built the same way. Returns the executable's path."""
-    return _build_sanitize_program("mxs_sanitize_reorder", SANITIZE_REORDER_SOURCES, verbose)
+# build_sanitize_ijoin(verbose=False) .. build_sanitize_reorder: the names the tests import.
+for _name in filter(None, SANITIZE_PROGRAMS):
+    globals()["build_sanitize_" + _name] = (
+        lambda verbose=False, _n=_name: build_sanitize_program(_n, verbose))
 
 
 TSAN_SOURCES = ["tests/tsan_main.cpp"]
@@ -288,13 +235,8 @@ def main(argv: list[str] | None = None) -> int:
         print(build_capi(verbose=True))
         return 0
     if a.sanitize:
-        print(build_sanitize(verbose=True))
-        print(build_sanitize_ijoin(verbose=True))
-        print(build_sanitize_lookup(verbose=True))
-        print(build_sanitize_timeout(verbose=True))
-        print(build_sanitize_sustain(verbose=True))
-        print(build_sanitize_burst(verbose=True))
-        print(build_sanitize_reorder(verbose=True))
+        for name in SANITIZE_PROGRAMS:
+            print(build_sanitize_program(name, verbose=True))
         return 0
     if a.tsan:
         print(build_tsan(verbose=True))

@@ -750,6 +750,18 @@ def join_plan(lkeys: torch.Tensor, lheads: torch.Tensor, ltotal: int, rkeys: tor
                     pairs, matched)
 
 
+def _pair_range(p0: int, p1: int, pairs: int) -> None:
+    """[p0, p1) must lie inside the plan's [0, pairs)."""
+    if not 0 <= p0 <= p1 <= pairs:
+        raise ValueError(f"pair range [{p0}, {p1}) outside [0, {pairs})")
+
+
+def _pair_columns(ncols: int, n: int, dev):
+    """`ncols` int64 output columns of n rows, every one 16-byte aligned (the expand kernels'
+    paired stores): the rows of one tensor whose row length is n rounded up to even."""
+    return torch.empty((ncols, n + (n & 1)), dtype=torch.int64, device=dev)[:, :n].unbind(0)
+
+
 def join_expand(jp: JoinPlan, lord: torch.Tensor, rord: torch.Tensor, p0: int, p1: int):
     """Pairs [p0, p1) of the planned firing as three int64 columns of p1 - p0 rows: the key id,
     the left value's and the right value's f64 bit patterns (`lord` / `rord`: the sides' order
@@ -758,15 +770,10 @@ def join_expand(jp: JoinPlan, lord: torch.Tensor, rord: torch.Tensor, p0: int, p
     p0, p1 = int(p0), int(p1)
     _check(lord, torch.int64, jp.ltotal, "lord", dev)
     _check(rord, torch.int64, jp.rtotal, "rord", dev)
-    if not 0 <= p0 <= p1 <= jp.pairs:
-        raise ValueError(f"pair range [{p0}, {p1}) outside [0, {jp.pairs})")
-    n = p1 - p0
-    out = torch.empty((3, n), dtype=torch.int64, device=dev)
-    if n == 0:
-        return out[0], out[1], out[2]
-    if n % 2:  # every column starts 16-byte aligned (the kernel's paired stores)
-        out = torch.empty((3, n + 1), dtype=torch.int64, device=dev)[:, :n]
-    ok, ol, orr = out[0], out[1], out[2]
+    _pair_range(p0, p1, jp.pairs)
+    ok, ol, orr = _pair_columns(3, p1 - p0, dev)
+    if p0 == p1:
+        return ok, ol, orr
     m = load()
     if _is_gpu(lord):
         m.gpu_join_expand(jp.plan.data_ptr(), jp.lkeys.numel(), jp.matched, jp.pairs,
@@ -877,12 +884,9 @@ def ijoin_expand(jp: IJoinPlan, p0: int, p1: int):
     partners in the other buffer's order."""
     dev = jp.lb.device
     p0, p1 = int(p0), int(p1)
-    if not 0 <= p0 <= p1 <= jp.pairs:
-        raise ValueError(f"pair range [{p0}, {p1}) outside [0, {jp.pairs})")
-    n = p1 - p0
-    out = torch.empty((4, n + (n & 1)), dtype=torch.int64, device=dev)[:, :n]  # 16-byte columns
-    ok, ol, orr, ot = out[0], out[1], out[2], out[3]
-    if n == 0:
+    _pair_range(p0, p1, jp.pairs)
+    ok, ol, orr, ot = _pair_columns(4, p1 - p0, dev)
+    if p0 == p1:
         return ok, ol, orr, ot
     bk, bt, bv = jp.batch
     _, ots, ov = jp.other
@@ -897,18 +901,23 @@ def ijoin_expand(jp: IJoinPlan, p0: int, p1: int):
     return ok, ol, orr, ot
 
 
+def _ijoin_out(out: torch.Tensor, rows: int, inputs, name: str) -> None:
+    """`out` must be a contiguous int64 [3, >= rows] tensor that shares no storage with `inputs`."""
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != 3 or out.shape[1] < rows \
+            or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous int64 [3, >= rows] tensor")
+    for c in inputs:
+        if c.numel() and c.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+            raise ValueError(f"{name}: out must not alias an input")
+
+
 def ijoin_merge(old, batch, out: torch.Tensor) -> int:
     """Merge the sorted `batch` into the sorted buffer `old` (both (key, ts, val)) into the rows
     of `out` (int64 [3, cap]); on equal (key, ts) the old rows stay first. Returns the row count."""
     dev = out.device
     no = _ijoin_cols(old, "old", dev)
     nb = _ijoin_cols(batch, "batch", dev)
-    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != 3 \
-            or out.shape[1] < no + nb or not out.is_contiguous():
-        raise ValueError("ijoin_merge: out must be a contiguous int64 [3, >= rows] tensor")
-    for c in (*old, *batch):
-        if c.numel() and c.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
-            raise ValueError("ijoin_merge: out must not alias an input")
+    _ijoin_out(out, no + nb, (*old, *batch), "ijoin_merge")
     cuda = _is_gpu(out)
     load().ijoin_merge(cuda, *(_p(c) for c in old), no, *(_p(c) for c in batch), nb,
                        _p(out[0]), _p(out[1]), _p(out[2]), _stream(out) if cuda else 0)
@@ -920,12 +929,7 @@ def ijoin_purge(src, cutoff: int, out: torch.Tensor) -> int:
     rows of `out` (int64 [3, cap >= rows]). Returns the number of survivors (one readback)."""
     dev = out.device
     n = _ijoin_cols(src, "src", dev)
-    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != 3 or out.shape[1] < n \
-            or not out.is_contiguous():
-        raise ValueError("ijoin_purge: out must be a contiguous int64 [3, >= rows] tensor")
-    for c in src:
-        if c.numel() and c.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
-            raise ValueError("ijoin_purge: out must not alias an input")
+    _ijoin_out(out, n, src, "ijoin_purge")
     m = load()
     if not _is_gpu(out):
         return m.cpu_ijoin_purge(*(_p(c) for c in src), n, int(cutoff), _p(out[0]), _p(out[1]),

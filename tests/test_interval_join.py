@@ -510,3 +510,44 @@ def test_gpu_pairs_beyond_32_bits_and_scan_carry(gpu_device):
 @pytest.mark.parametrize("lo,hi", [(-3, 5), (2, 7), (0, 0), (0, 3), (-3, 0)])
 def test_gpu_operator_equals_model(gpu_device, lo, hi):
     _engine_vs_model(lo, hi, dev=gpu_device, steps=20, seed=9, chunk=5, snapshot_at=11)
+
+
+# ---- GPU: the scan's tile seams and the expand's ---------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("ends", [0, 3], ids=["ends-empty", "ends-nonempty"])
+@pytest.mark.parametrize("n", [1, 4095, 4096, 4097])
+def test_gpu_scan_tile_seams_equal_the_twin(gpu_device, n, ends):
+    rng = np.random.default_rng(n)
+    cnt = rng.integers(0, 4, n).astype(np.int64) * (rng.random(n) < 0.5)
+    cnt[0] = cnt[-1] = ends
+    lb = rng.integers(0, 1 << 40, n).astype(np.int64)
+    want = K.ijoin_scan(T(cnt), T(lb))
+    got = K.ijoin_scan(T(cnt, gpu_device), T(lb, gpu_device))
+    assert got[1:] == want[1:] and want[3] == 0
+    _check_scan(cnt, lb, want[0], *want[1:3])
+    _check_scan(cnt, lb, got[0], *got[1:3])
+
+
+_SEAM_RANGES = [(0, 4097), (0, 1), (0, 2), (1, 2), (1, 3), (4095, 4096), (4095, 4097),
+                (4096, 4097), (4097, 4098), (1, 4098), (4111, 8208), (4097, 8194), (0, 8208)]
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_case():
+    """A plan row of exactly one expand tile (4096 pairs), then one of 1 pair, three of 5 and
+    another of 4096: P = 8208."""
+    other = [(0, 0, 10_000 + i) for i in range(4096)] + [(1, 0, 20_000)]
+    other += [(2, 0, 30_000 + i) for i in range(5)] + [(3, 0, 40_000 + i) for i in range(4096)]
+    batch = [(0, 0, 1), (1, 0, 2)] + [(2, 0, 100 + i) for i in range(3)] + [(3, 0, 3)]
+    return cols(batch), cols(other)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("side", [0, 1])
+def test_gpu_expand_tile_seams_equal_the_twin(gpu_device, side):
+    batch, other = _seam_case()
+    cj = K.ijoin_plan(side, batch, other, 0, 0)
+    assert cj.plan[:7].tolist() == [0, 4096, 4097, 4102, 4107, 4112, 8208]
+    gj = K.ijoin_plan(side, _gpu_cols(batch, gpu_device), _gpu_cols(other, gpu_device), 0, 0)
+    for p0, p1 in _SEAM_RANGES:  # lengths 1, 2 and 4097, even and odd starts, whole tiles
+        np.testing.assert_array_equal(expand(gj, p0, p1), expand(cj, p0, p1), str((p0, p1)))

@@ -325,3 +325,35 @@ def test_gpu_operator_equals_cpu_operator(gpu_device, size, slide, lateness):
     _, g, _ = _run_op(gpu_device, k, t, v, size=size, slide=slide, lateness=lateness, steps=8)
     _, c, _ = _run_op("cpu", k, t, v, size=size, slide=slide, lateness=lateness, steps=8)
     assert len(c) > 500 and sorted(g) == sorted(c)
+
+
+def _lw_scan(counts: np.ndarray, kmin: int, dev):
+    """lw_scan of the key counts: (offs, heads, head_keys) with the heads cut to their number."""
+    m, nk = K.load(), counts.size
+    c = torch.from_numpy(counts.astype(np.int32)).to(dev)
+    cuda = c.is_cuda
+    offs = torch.empty(nk + 1, dtype=torch.int64, device=dev)
+    heads = torch.full((nk,), -1, dtype=torch.int64, device=dev)
+    hkeys = torch.full((nk,), -1, dtype=torch.int64, device=dev)
+    nh = torch.zeros(1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(max(16, m.lw_scan_scratch_bytes(nk)), dtype=torch.uint8, device=dev)
+    m.lw_scan(cuda, c.data_ptr(), nk, kmin, scratch.data_ptr(), offs.data_ptr(), heads.data_ptr(),
+              hkeys.data_ptr(), nh.data_ptr(), torch.cuda.current_stream().cuda_stream if cuda else 0)
+    k = int(nh.item())
+    return offs.cpu(), heads[:k].cpu(), hkeys[:k].cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ends", [0, 3], ids=["ends-empty", "ends-nonempty"])
+@pytest.mark.parametrize("n", [1, 4095, 4096, 4097])
+def test_gpu_key_scan_tile_seams_equal_the_twin(gpu_device, n, ends):
+    rng = np.random.default_rng(n)
+    counts = rng.integers(0, 4, n) * (rng.random(n) < 0.5)
+    counts[0] = counts[-1] = ends
+    want, got = _lw_scan(counts, 1000, "cpu"), _lw_scan(counts, 1000, gpu_device)
+    ne = np.nonzero(counts)[0]
+    excl = np.concatenate([[0], np.cumsum(counts)])
+    assert np.array_equal(want[0].numpy(), excl) and np.array_equal(want[2].numpy(), 1000 + ne)
+    assert np.array_equal(want[1].numpy(), excl[ne])
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)

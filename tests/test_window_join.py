@@ -476,3 +476,65 @@ def test_gpu_operator_equals_cpu_operator(gpu_device, size, slide):
         assert np.array_equal(got[s], want[s]), s
     assert gpu.metrics.num_late_records_dropped == cpu.metrics.num_late_records_dropped > 0
     assert gpu.pairs_out == cpu.pairs_out > 10 ** 5
+
+
+# ---- 15. GPU: the scan's tile seams and its carry round ----------------------------------------
+def _unit_plan(matched: np.ndarray, dev):
+    """Left segments of one element each (keys 0 .. n - 1); the right side has the keys that
+    `matched` marks, two elements each, and one key beyond the left side's."""
+    n = matched.size
+    rk = np.concatenate([np.nonzero(matched)[0], [n + 5]]).astype(np.int64)
+    ar = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+    return K.join_plan(ar(np.arange(n)), ar(np.arange(n)), n, ar(rk), ar(np.arange(rk.size) * 2),
+                       2 * rk.size)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ends", [False, True], ids=["ends-empty", "ends-matched"])
+@pytest.mark.parametrize("n", [1, 4095, 4096, 4097])
+def test_gpu_scan_tile_seams_equal_the_twin(gpu_device, n, ends):
+    matched = np.arange(n) % 3 == 1
+    matched[0] = matched[-1] = ends
+    want, got = _unit_plan(matched, "cpu"), _unit_plan(matched, gpu_device)
+    m = int(matched.sum())
+    assert (got.pairs, got.matched) == (want.pairs, want.matched) == (2 * m, m)
+    for a, b in zip(_plan_arrays(got), _plan_arrays(want)):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+def test_gpu_scan_carry_round_equals_the_twin(gpu_device):
+    """4096 * 1024 + 1 left segments are 1025 scan tiles: the one workgroup that scans the tile
+    totals takes 1024 of them per round, so the last tile's offsets come from the carry."""
+    n = 4096 * 1024 + 1
+    matched = np.arange(n) % 2 == 0
+    want, got = _unit_plan(matched, "cpu"), _unit_plan(matched, gpu_device)
+    assert (got.pairs, got.matched) == (want.pairs, want.matched) == (n + 1, (n + 1) // 2)
+    for a, b in zip(_plan_arrays(got), _plan_arrays(want)):
+        assert torch.equal(a, b)
+
+
+# ---- 16. GPU: the expand's tile seams ------------------------------------------------------------
+_SEAM_RANGES = [(0, 4097), (0, 1), (0, 2), (1, 2), (1, 3), (4095, 4096), (4095, 4097),
+                (4096, 4097), (4097, 4098), (1, 4098), (4111, 8208), (4097, 8194), (0, 8208)]
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_case():
+    """A segment of exactly one expand tile (64 x 64 = 4096 pairs), then one of 1 pair, one of
+    3 x 5 and another of 4096: P = 8208."""
+    rng = np.random.default_rng(16)
+    l = Side([0, 1, 2, 3], [64, 1, 3, 64], _values(rng, 132))
+    r = Side([0, 1, 2, 3], [64, 1, 5, 64], _values(rng, 134))
+    return l, r
+
+
+@pytest.mark.gpu
+def test_gpu_expand_tile_seams_equal_the_twin(gpu_device):
+    l, r = _seam_case()
+    jp = _plan(l, r)
+    assert jp.pair_off.tolist() == [0, 4096, 4097, 4112, 8208]
+    gl, gr = l.to(gpu_device), r.to(gpu_device)
+    gp = _plan(gl, gr)
+    for p0, p1 in _SEAM_RANGES:  # lengths 1, 2 and 4097, even and odd starts, whole tiles
+        assert np.array_equal(_expand(gp, gl, gr, p0, p1), _expand(jp, l, r, p0, p1)), (p0, p1)
