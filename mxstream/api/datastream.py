@@ -108,10 +108,22 @@ class DataStream:
 
     def connect(self, other: "DataStream"):
         """Connected streams (api/connect.py): ``a.connect(b)[.key_by(k1, k2)].process(fn)``;
-        keyed at once when both inputs are keyed streams."""
+        keyed at once when both inputs are keyed streams. With a ``BroadcastStream``
+        (``rules.broadcast(descriptor)``): broadcast state (api/broadcast.py), keyed when this
+        stream is."""
+        from .broadcast import BroadcastConnectedStream, BroadcastStream
         from .connect import ConnectedStreams
 
+        if isinstance(other, BroadcastStream):
+            return BroadcastConnectedStream(self, other)
         return ConnectedStreams(self, other)
+
+    def broadcast(self, *descriptors):
+        """A ``BroadcastStream`` that carries the ``MapStateDescriptor``s of the broadcast state
+        its elements are kept in (api/broadcast.py)."""
+        from .broadcast import BroadcastStream
+
+        return BroadcastStream(self, descriptors)
 
     def rebalance(self) -> "DataStream":
         return self._one_input("Rebalance", lambda: O.RebalanceOp(self.env.config.rebalance_start))

@@ -456,6 +456,204 @@ class LookupLatest(CoProcessFunction):
             out.collect(Tuple3(ctx.get_current_key(), v, t))
 
 
+_NO_BROADCAST_STATE = (
+    "The requested state does not exist. Check for typos in your state descriptor, or specify "
+    "the state descriptor in the datastream.broadcast(...) call if you forgot to register it.")
+
+
+class _BaseBroadcastProcessFunction(RichFunction):
+    """What BroadcastProcessFunction and KeyedBroadcastProcessFunction share (Flink 1.8
+    ``BaseBroadcastProcessFunction``): process_element(value, ctx, out) for the first input with
+    a read-only view of the broadcast state, process_broadcast_element(value, ctx, out) for the
+    broadcast input, which alone may change it. The operator (runtime/operators.py
+    BroadcastProcessOp) calls process_broadcast_element once per parallel instance, each with
+    that instance's copy of the state."""
+
+    class Context:
+        """The broadcast side: the state is read-write."""
+
+        _read_only = False
+
+        def __init__(self, ts, states: dict, side_outputs, watermark, clock):
+            self._ts = ts
+            self._states = states        # descriptor name -> this instance's entries
+            self._side = side_outputs
+            self._wm, self._clock = watermark, clock
+
+        def get_broadcast_state(self, descriptor):
+            from .state import BroadcastState, ReadOnlyBroadcastState
+
+            entries = self._states.get(getattr(descriptor, "name", None))
+            if entries is None:
+                raise ValueError(_NO_BROADCAST_STATE)
+            return (ReadOnlyBroadcastState if self._read_only else BroadcastState)(entries)
+
+        def timestamp(self):
+            return self._ts
+
+        def current_watermark(self):
+            return self._wm()
+
+        def current_processing_time(self):
+            return self._clock()
+
+        def output(self, tag, value):
+            self._side.setdefault(tag.tag_id, []).append(value)
+
+        getBroadcastState = get_broadcast_state
+        currentWatermark = current_watermark
+        currentProcessingTime = current_processing_time
+
+    class ReadOnlyContext(Context):
+        """The element side: the state is read-only."""
+
+        _read_only = True
+
+    def process_element(self, value, ctx, out: Collector):
+        raise NotImplementedError
+
+    def process_broadcast_element(self, value, ctx, out: Collector):
+        raise NotImplementedError
+
+    def processElement(self, value, ctx, out):
+        return self.process_element(value, ctx, out)
+
+    def processBroadcastElement(self, value, ctx, out):
+        return self.process_broadcast_element(value, ctx, out)
+
+
+class BroadcastProcessFunction(_BaseBroadcastProcessFunction):
+    """``stream.connect(rules.broadcast(descriptor)).process(fn)`` on a non-keyed first input: no
+    keyed state, no timers, no key."""
+
+
+class KeyedBroadcastProcessFunction(_BaseBroadcastProcessFunction):
+    """``stream.key_by(k).connect(rules.broadcast(descriptor)).process(fn)``: the element side
+    also has keyed state, a timer service and the current key; the broadcast side may visit the
+    keyed state of every key (``apply_to_keyed_state``); on_timer(timestamp, ctx, out) sees the
+    read-only broadcast state."""
+
+    class Context(_BaseBroadcastProcessFunction.Context):
+        def __init__(self, ts, states, side_outputs, watermark, clock, apply):
+            super().__init__(ts, states, side_outputs, watermark, clock)
+            self._apply = apply
+
+        def apply_to_keyed_state(self, state_descriptor, fn):
+            """``fn(key, state)`` for every key of this parallel instance that has the state."""
+            self._apply(state_descriptor, fn)
+
+        applyToKeyedState = apply_to_keyed_state
+
+    class ReadOnlyContext(_BaseBroadcastProcessFunction.ReadOnlyContext):
+        def __init__(self, ts, states, side_outputs, watermark, clock, timer_service, key):
+            super().__init__(ts, states, side_outputs, watermark, clock)
+            self._timers, self._key = timer_service, key
+
+        def timer_service(self):
+            return self._timers
+
+        def get_current_key(self):
+            return self._key
+
+        timerService = timer_service
+        getCurrentKey = get_current_key
+
+    class OnTimerContext(ReadOnlyContext):
+        def __init__(self, ts, states, side_outputs, watermark, clock, timer_service, key,
+                     time_domain):
+            super().__init__(ts, states, side_outputs, watermark, clock, timer_service, key)
+            self.time_domain = time_domain
+
+        timeDomain = property(lambda self: self.time_domain)
+
+    def on_timer(self, timestamp: int, ctx, out: Collector):
+        pass
+
+    def onTimer(self, timestamp, ctx, out):
+        return self.on_timer(timestamp, ctx, out)
+
+
+class RuleSetAlert(KeyedBroadcastProcessFunction):
+    """A rule set that holds for every key, changed while the job runs, over
+    ``samples.key_by(k).connect(rules.broadcast(RuleSetAlert.DESCRIPTOR))``. A rule
+    ``(id, when, threshold)`` of the broadcast input is stored as ``id -> (when, threshold)`` in
+    the broadcast state, the last rule of an id wins, ``when`` None withdraws the rule and nothing
+    is emitted. A sample collects, for the rules in ascending id, ``Tuple4(key,
+    sample[value_field], id, threshold)`` with the sample's timestamp where
+    ``sample[value_field] <when> threshold`` holds. `when` is one of ``">", ">=", "<", "<=", "==",
+    "!="``; values and thresholds are int or float (not bool) and compare as Java compares
+    doubles: a NaN on either side is false for every operator but ``!=``, and ``-0.0 == 0.0``.
+    Warning at 80, critical at 95, suspiciously idle below 1:
+
+        samples.key_by(0).connect(rules.broadcast(RuleSetAlert.DESCRIPTOR)) \\
+            .process(RuleSetAlert(2)).print()
+        # rules:  (1, ">", 80.0)  (2, ">", 95.0)  (3, "<", 1.0)  ...  (1, None, 0) withdraws rule 1
+        # (host, usage, rule id, threshold): one line per sample and rule that the sample breaks
+
+    The planner runs exactly this class (not a subclass) with a positional key on the device
+    rule-set operator (runtime/ruleset_operator.py); these methods are the exact host
+    implementation used otherwise."""
+
+    class _RuleSetDescriptor:
+        """``MapStateDescriptor("rule-set")``, made at first use (api/state.py imports this
+        module)."""
+
+        def __get__(self, obj, cls):
+            from .state import MapStateDescriptor
+
+            RuleSetAlert.DESCRIPTOR = MapStateDescriptor("rule-set")
+            return RuleSetAlert.DESCRIPTOR
+
+    DESCRIPTOR = _RuleSetDescriptor()
+
+    def __init__(self, value_field: int, id_field: int = 0, when_field: int = 1,
+                 threshold_field: int = 2):
+        for name, f in (("value_field", value_field), ("id_field", id_field),
+                        ("when_field", when_field), ("threshold_field", threshold_field)):
+            if isinstance(f, bool) or not isinstance(f, int) or f < 0:
+                raise ValueError(f"RuleSetAlert: {name} is a non-negative int, got {f!r}")
+        self.value_field, self.id_field = value_field, id_field
+        self.when_field, self.threshold_field = when_field, threshold_field
+        self.native = ("ruleset", value_field, id_field, when_field, threshold_field)
+
+    @staticmethod
+    def _number(x, what: str):
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise TypeError(f"RuleSetAlert: {what} must be an int or a float, got {x!r}")
+        return x
+
+    def parse_rule(self, rule):
+        """``(id, when, threshold)`` of a broadcast element, validated."""
+        rid, when = rule[self.id_field], rule[self.when_field]
+        if isinstance(rid, bool) or not isinstance(rid, int):
+            raise TypeError(f"RuleSetAlert: the rule id must be an int, got {rid!r}")
+        if when is not None and (not isinstance(when, str) or when not in _LOOKUP_WHENS):
+            raise ValueError("RuleSetAlert: when must be one of '>', '>=', '<', '<=', '==', '!=' "
+                             f"or None, got {when!r}")
+        return rid, when, self._number(rule[self.threshold_field], "the rule's threshold")
+
+    def process_broadcast_element(self, rule, ctx, out):
+        rid, when, threshold = self.parse_rule(rule)
+        state = ctx.get_broadcast_state(self.DESCRIPTOR)
+        if when is None:
+            state.remove(rid)
+        else:
+            state.put(rid, (when, threshold))
+
+    def process_element(self, sample, ctx, out):
+        from .tuples import Tuple4
+
+        rules = ctx.get_broadcast_state(self.DESCRIPTOR).immutable_entries()
+        if not rules:
+            return
+        v = self._number(sample[self.value_field], "the sample's value")
+        key = ctx.get_current_key()
+        for rid, (when, threshold) in sorted(rules, key=lambda e: e[0]):
+            # Python compares an int with a float exactly; Java compares the two doubles
+            if _LOOKUP_WHENS[when](float(v), float(threshold)):
+                out.collect(Tuple4(key, v, rid, threshold))
+
+
 class CountWithTimeout(KeyedProcessFunction):
     """Per-key element count with an event-time timeout (the ``CountWithTimeoutFunction`` of
     Flink's ProcessFunction documentation): every element adds one to its key's count, stores its

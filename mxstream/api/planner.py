@@ -22,6 +22,9 @@ positional keys and such a projection is lowered onto NativeIntervalJoinOp
 (``_lower_interval_join``); any other keeps the tagged union -> keyed IntervalJoinOp.
 ``a.connect(b).key_by(p, q).process(LookupLatest(..))`` with positional keys is lowered onto
 NativeLookupOp (``_lower_connect``); every other connected function keeps the host operators.
+``a.key_by(p).connect(b.broadcast(..)).process(RuleSetAlert(..))`` is lowered onto
+NativeRuleSetOp (``_lower_broadcast_connect``); every other broadcast function keeps
+BroadcastProcessOp.
 ``key_by(p).process(CountWithTimeout(..))`` is lowered onto NativeTimeoutOp and
 ``key_by(p).process(SustainedAlert(..))`` onto NativeSustainOp and
 ``key_by(p).process(BurstAlert(..))`` with ``times <= 16`` onto NativeBurstOp
@@ -305,6 +308,9 @@ def plan(env, sinks):
             continue
         if meta.get("kind") == "connect":
             _lower_connect(env, t, meta)
+            continue
+        if meta.get("kind") == "broadcast_connect":
+            _lower_broadcast_connect(env, t, meta)
             continue
         if meta.get("kind") == "keyed_process":
             _lower_keyed_process(env, t, meta)
@@ -967,6 +973,31 @@ def _lower_connect(env, t, meta) -> None:
     def factory():
         return NativeLookupOp(fn=fn, key_pos=kp, val_pos=val_pos, ok_arities=arities,
                               device=device, fallback_factory=fallback)
+
+    t.factory = factory
+    t.meta = dict(t.meta, native=True)
+    meta["columnar"]["on"] = True  # the tag operators let column batches through as they are
+
+
+def _lower_broadcast_connect(env, t, meta) -> None:
+    """``a.key_by(p).connect(b.broadcast(RuleSetAlert.DESCRIPTOR)).process(fn)`` ->
+    NativeRuleSetOp when `fn` is exactly a ``RuleSetAlert`` (not a subclass, whose methods may
+    differ), the first input is keyed by a field position and one rank runs the job. Anything
+    else -- any other function, a key selector, the non-keyed form -- keeps the host
+    BroadcastProcessOp."""
+    from ..runtime.native_ops import NativeRuleSetOp
+    from . import functions as F
+
+    fn, kp = meta["fn"], meta["key_pos"]
+    comm = getattr(env, "_comm", None)
+    world = comm.world if comm is not None else getattr(env, "world", 1)
+    if type(fn) is not F.RuleSetAlert or kp is None or world > 1:
+        return
+    fallback = t.factory
+    device = env.config.device
+
+    def factory():
+        return NativeRuleSetOp(fn=fn, key_pos=kp, device=device, fallback_factory=fallback)
 
     t.factory = factory
     t.meta = dict(t.meta, native=True)

@@ -205,6 +205,53 @@ class AggregatingState(_StateBase):
             t[(key, target)] = acc if cur is None else self._merge(cur, acc)
 
 
+class BroadcastState:
+    """Broadcast state (Flink 1.8 ``BroadcastState``): a map that every parallel instance of the
+    operator holds a copy of (runtime/operators.py BroadcastProcessOp). Read-write on the
+    broadcast side of a (Keyed)BroadcastProcessFunction."""
+
+    def __init__(self, entries: dict):
+        self._m = entries
+
+    def get(self, key):
+        return self._m.get(key)
+
+    def contains(self, key) -> bool:
+        return key in self._m
+
+    def immutable_entries(self):
+        return tuple(self._m.items())
+
+    def put(self, key, value) -> None:
+        self._m[key] = value
+
+    def put_all(self, d: dict) -> None:
+        self._m.update(d)
+
+    def remove(self, key) -> None:
+        self._m.pop(key, None)
+
+    def entries(self):
+        return list(self._m.items())
+
+    def clear(self) -> None:
+        self._m.clear()
+
+    putAll = put_all
+    immutableEntries = immutable_entries
+
+
+class ReadOnlyBroadcastState(BroadcastState):
+    """The element side's view (``ReadOnlyBroadcastState``): get, contains and
+    immutable_entries; a write raises TypeError."""
+
+    def _read_only(self, *_a, **_k):
+        raise TypeError("the broadcast state is read-only on the element side: it may only be "
+                        "changed in process_broadcast_element")
+
+    put = put_all = remove = entries = clear = putAll = _read_only
+
+
 _STATE_CLASSES = {"value": ValueState, "list": ListState, "map": MapState,
                   "reducing": ReducingState, "aggregating": AggregatingState}
 

@@ -1072,6 +1072,98 @@ def config15(steps: int, warmup: int, batch: int | None = None, keys: int = 1_00
             "table_rows": op.cap, "steps": steps, "device": str(dev)}
 
 
+def config20(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             rules: int = 8, dense: bool = False, device: str = "cuda") -> dict:
+    """Broadcast rule set at scale (``samples.key_by(0).connect(rules.broadcast(..)).process(
+    RuleSetAlert(..))``): config 15's samples (`batch` device-generated samples per step, values
+    uniform in [0, 10000)) are tested against `rules` rules of RuleSetOperator, fed directly. Rule
+    r is ``> 9900 + 10 r``: about 5 % rows per sample at 8 rules; two rules move every step, as a
+    rule stream would move them while the job runs. With `dense` rule r is ``> -1 - r``: every
+    sample breaks every rule, the expansion-bound case. The rows leave the device operator as
+    five int64 columns.
+
+    Timed per step, each behind a device synchronise, alternating in the same call: the native
+    step (rule update + probe) and a yardstick that is not the code under test, the torch
+    composition: an ``n x R`` compare, ``nonzero`` (row-major: sample order, then rule id), five
+    index gathers. The sample generation is outside both windows."""
+    from ..runtime.ruleset_operator import RuleSetOperator
+
+    if not 1 <= rules <= K.RULESET_MAX:
+        raise ValueError(f"config 20: 1 .. {K.RULESET_MAX} rules")
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    op = RuleSetOperator(dev)
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    gt = K.LOOKUP_WHENS[">"]
+
+    def threshold(r: int, i: int) -> float:
+        moved = float((i + r) % 5)           # a rule that moves takes one of five values
+        return -1.0 - r - moved if dense else 9_900.0 + 10 * r + moved
+
+    def bits_of(xs) -> np.ndarray:
+        return np.asarray(xs, dtype=np.float64).view(np.int64)
+
+    current = [threshold(r, 0) for r in range(rules)]
+    op.update(np.arange(rules), np.full(rules, gt), bits_of(current))
+    ids = torch.arange(rules, dtype=torch.int64, device=dev)
+    sk, st, sv = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3))
+    state = {"i": 0}
+    native_ms: list[float] = []
+    torch_ms: list[float] = []
+
+    def yardstick():
+        thr_bits = torch.from_numpy(bits_of(current)).to(dev)
+        mask = sv.view(torch.float64)[:, None] > thr_bits.view(torch.float64)[None, :]
+        idx = mask.nonzero()
+        s, r = idx[:, 0], idx[:, 1]
+        return sk[s], sv[s], ids[r], thr_bits[r], st[s]
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, sv, seed=20, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=0,
+                     val_span=10_000, val_f64=True)
+        moving = sorted({i % rules, (i + 1) % rules})
+        for r in moving:
+            current[r] = threshold(r, i + 1)
+        _sync(dev)
+        t_in = time.perf_counter()
+        op.process(1, np.asarray(moving), np.full(len(moving), gt),
+                   bits_of([current[r] for r in moving]))
+        out = op.process(0, sk, st, sv)
+        _sync(dev)
+        native_ms.append((time.perf_counter() - t_in) * 1e3)
+        rows = sum(int(o[0].numel()) for o in out)
+        t_in = time.perf_counter()
+        ref = yardstick()
+        _sync(dev)
+        torch_ms.append((time.perf_counter() - t_in) * 1e3)
+        got = [torch.cat([o[c] for o in out]) for c in range(5)] if out else None
+        if int(ref[0].numel()) != rows or (out and not all(
+                torch.equal(a, b) for a, b in zip(got, ref))):
+            raise RuntimeError("config 20: the native probe and the torch composition differ")
+        state["i"] = i + 1
+        return rows
+
+    for _ in range(warmup):
+        step()
+    native_ms.clear()
+    torch_ms.clear()
+    rows = 0
+    for _ in range(steps):
+        rows += step()
+    nat, ref = _spread(native_ms), _spread(torch_ms)
+    return {"config": 20, "metric": "events/sec (broadcast rule set, samples probed)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "native_ms": nat, "torch_ms": ref,
+            "torch_events_per_s": batch / ref["median"] * 1e3,
+            "native_over_torch_time": nat["median"] / ref["median"],
+            "rows": rows, "rows_per_step": rows // max(1, steps),
+            "rows_per_sample": rows / max(1, steps * batch), "rules": rules, "dense": dense,
+            "samples_per_step": batch, "steps": steps, "device": str(dev)}
+
+
 def config16(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
              timeout_ms: int = 3_000, zipf: float = 0.0, device: str = "cuda") -> dict:
     """Keyed event-time timers at scale (``samples.key_by(0).process(CountWithTimeout(..))``):
@@ -1756,7 +1848,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1789,6 +1881,10 @@ def main(argv=None) -> int:
     ap.add_argument("--disorder-ms", type=int, default=3_000,
                     help="config 19: timestamps are displaced backwards uniformly within this "
                          "span, and the watermark runs this far behind (0: an in-order stream)")
+    ap.add_argument("--rules", type=int, default=8,
+                    help="config 20: rules in force (1 .. 64); rule r is > 9900 + 10 r")
+    ap.add_argument("--dense", action="store_true",
+                    help="config 20: every sample breaks every rule (the expansion-bound case)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None,
@@ -1880,6 +1976,9 @@ def main(argv=None) -> int:
     elif a.config == 19:
         r = config19(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, for_ms=a.for_ms,
                      disorder_ms=a.disorder_ms, zipf=a.zipf, device=a.device)
+    elif a.config == 20:
+        r = config20(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, rules=a.rules,
+                     dense=a.dense, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

@@ -1088,6 +1088,74 @@ def lookup_gather(table: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, t
     return out[0], out[1], out[2], out[3]
 
 
+# ---- broadcast rule set (csrc/mxs_ruleset.h) ---------------------------------------------------
+
+RULESET_MAX = 64  # rule ids [0, 64): one mask bit each
+
+
+def _ruleset_table(rules: torch.Tensor) -> None:
+    if rules.dtype != torch.int64:
+        raise TypeError(f"ruleset: the rule table is int64, got {rules.dtype}")
+    if tuple(rules.shape) != (RULESET_MAX, 2) or not rules.is_contiguous() \
+            or rules.data_ptr() % 16:
+        raise ValueError("ruleset: the rule table must be a contiguous, 16-byte aligned int64 "
+                         f"[{RULESET_MAX}, 2] tensor")
+
+
+@dataclass
+class RuleSetCount:
+    """A counted sample batch (``ruleset_count``): what ``ruleset_emit`` needs to write the rows."""
+    rules: torch.Tensor
+    vals: torch.Tensor
+    gsum: torch.Tensor      # int32 [ntiles * 64]: rows per group of 64 samples
+    counts: torch.Tensor    # int32 [ntiles]: rows per tile
+    offsets: torch.Tensor   # int64 [ntiles]: exclusive scan of counts
+    total: int
+
+
+def ruleset_count(rules: torch.Tensor, vals: torch.Tensor) -> RuleSetCount:
+    """Test a batch of samples against the rule table (row r = threshold bits, comparison code
+    1..6, 0: no rule r): the rows (sample, broken rule) per group of 64 samples and per tile, the
+    tiles' exclusive scan and the total (one readback)."""
+    dev = rules.device
+    _ruleset_table(rules)
+    n = _lookup_cols((vals,), ("vals",), dev)
+    m = load()
+    ntiles = (n + m.LOOKUP_TILE - 1) // m.LOOKUP_TILE
+    gsum = torch.empty(max(1, ntiles * m.RULESET_GROUPS), dtype=torch.int32, device=dev)
+    counts = torch.empty(max(1, ntiles), dtype=torch.int32, device=dev)
+    offsets = torch.empty(max(1, ntiles), dtype=torch.int64, device=dev)
+    meta = torch.zeros(m.LOOKUP_META, dtype=torch.int64, device=dev)
+    cuda = _is_gpu(rules)
+    st = _stream(rules) if cuda else 0
+    m.ruleset_count(cuda, _p(vals), n, _p(rules), _p(gsum), _p(counts), st)
+    m.lookup_scan(cuda, _p(counts), ntiles, _p(offsets), _p(meta), st)
+    total = int(meta[0].item())
+    return RuleSetCount(rules, vals, gsum[:ntiles * m.RULESET_GROUPS], counts[:ntiles],
+                        offsets[:ntiles], total)
+
+
+def ruleset_emit(rc: RuleSetCount, keys: torch.Tensor, ts: torch.Tensor):
+    """The rows of a counted batch, in sample order, then ascending rule id, as five int64
+    columns: key id, value bits, rule id, threshold bits and timestamp."""
+    dev = rc.rules.device
+    _ruleset_table(rc.rules)
+    n = _lookup_cols((rc.vals, keys, ts), ("vals", "keys", "ts"), dev)
+    if not 0 <= rc.total <= n * RULESET_MAX:
+        raise ValueError("ruleset_emit: rows outside [0, 64 n]")
+    ntiles = (n + LOOKUP_TILE - 1) // LOOKUP_TILE
+    _check(rc.gsum, torch.int32, ntiles * (LOOKUP_TILE // 64), "gsum", dev)
+    _check(rc.counts, torch.int32, ntiles, "counts", dev)
+    _check(rc.offsets, torch.int64, ntiles, "offsets", dev)
+    out = torch.empty((5, rc.total), dtype=torch.int64, device=dev)
+    if rc.total:
+        cuda = _is_gpu(rc.rules)
+        load().ruleset_emit(cuda, _p(keys), _p(rc.vals), _p(ts), n, _p(rc.rules), _p(rc.gsum),
+                            _p(rc.counts), _p(rc.offsets), rc.total, *(_p(out[c]) for c in range(5)),
+                            _stream(rc.rules) if cuda else 0)
+    return out[0], out[1], out[2], out[3], out[4]
+
+
 # ---- keyed event-time timers (csrc/mxs_timeout.h) -----------------------------------------------
 
 TIMEOUT_TILE = 4096

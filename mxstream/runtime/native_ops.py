@@ -2459,6 +2459,103 @@ class NativeLookupOp(_NativeTwoSidedOp):
         super().restore(snap)
 
 
+class NativeRuleSetOp(_NativeTwoSidedOp):
+    """``samples.key_by(p).connect(rules.broadcast(RuleSetAlert.DESCRIPTOR)).process(
+    RuleSetAlert(..))`` on the device rule-set operator (runtime/ruleset_operator.py;
+    planner._lower_broadcast_connect). Side 0 is the samples and takes what the base class gives:
+    records, host and device column batches, the operator-owned key dictionary, integer values as
+    ``float(x)`` bits up to 2**53 that come back as longs. Side 1 is the rules: few, so its items
+    are expanded to records and handled on the host, and the threshold's kind (int or float) is
+    fixed by the first rule. The pending items are fed as runs of one side in arrival order (as
+    _feed_runs does) -- a run of rules updates the table, a run of samples is probed -- which is
+    what the per-record BroadcastProcessOp computes, in the same output order: every copy of its
+    broadcast state holds the same rules, so one table stands for all of them. Every probe slice
+    comes out as one host ColumnBatch ``(key, value, rule id, threshold)`` with the samples'
+    timestamps and the subtasks of their keys. A watermark emits nothing and is forwarded. A rule
+    id outside [0, 64), mixed threshold kinds, an integer beyond 2**53 and a non-numeric value
+    are unsupported data: the host operator before native state exists, an error afterwards."""
+
+    name = "Co-Process-Broadcast(native rule set)"
+
+    def __init__(self, *, fn, key_pos: int, row_chunk: int = 1 << 24, **kw):
+        arities = range(max(key_pos, fn.value_field) + 1, 1 << 16)
+        super().__init__(key_pos=(key_pos, None), val_pos=(fn.value_field, fn.threshold_field),
+                         layout=("k", "l", "id", "r"), ok_arities=(arities, ()), **kw)
+        self.fn = fn
+        self.fn_spec = (fn.value_field, fn.id_field, fn.when_field, fn.threshold_field)
+        self.row_chunk = int(row_chunk)
+
+    def _build(self) -> None:
+        from .ruleset_operator import RuleSetOperator
+
+        self.op = RuleSetOperator(device=torch.device(self.device), row_chunk=self.row_chunk)
+
+    # -- side 1: rules as (ids, comparison codes, threshold bits), on the host -------------------
+    def _recs_columns(self, side: int, recs: list, kinds: list):
+        if side == 0:
+            return super()._recs_columns(side, recs, kinds)
+        n = len(recs)
+        ids, codes = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+        thr = np.zeros(n, dtype=np.float64)
+        for i, r in enumerate(recs):
+            rid, when, t = self.fn.parse_rule(r.value[1])  # the host function's own errors
+            if not 0 <= rid < K.RULESET_MAX:
+                raise TypeError("rule id outside the device table")
+            ids[i], codes[i] = rid, K.LOOKUP_WHENS[when]
+            if when is None:
+                continue  # a withdrawal's threshold is not stored
+            self._kind(1, isinstance(t, float), kinds)
+            if not isinstance(t, float) and not -self._INT_EXACT <= t <= self._INT_EXACT:
+                raise TypeError("mixed value types")
+            thr[i] = t
+        return ids, codes, thr.view(np.int64)
+
+    def _batch_columns(self, side: int, cb: ColumnBatch, kinds: list):
+        if side == 0:
+            return super()._batch_columns(side, cb, kinds)
+        return self._recs_columns(1, cb.to_recs(), kinds)
+
+    def _feed(self, parts) -> list:
+        out, i = [], 0
+        while i < len(parts):
+            side, j = parts[i][0], i
+            while j < len(parts) and parts[j][0] == side:
+                j += 1
+            if side == 1:
+                self.op.process(1, *(np.concatenate([p[c] for p in parts[i:j]])
+                                     for c in (1, 2, 3)))
+            else:
+                cols = [torch.cat([self._to_dev(p[c]) for p in parts[i:j]]) for c in (1, 2, 3)]
+                out.extend(self._rows(*rows) for rows in self.op.process(0, *cols))
+            i = j
+        return out
+
+    def _rows(self, keys, vb, rid, tb, ts) -> ColumnBatch:
+        keys, vb, rid, tb, ts = (x.cpu().numpy() for x in (keys, vb, rid, tb, ts))
+        cols = [keys, None, rid, None]
+        kinds = [FK_STR if self.str_keys else FK_LONG, None, FK_LONG, None]
+        for f, bits, is_float in ((1, vb, self.is_float[0]), (3, tb, self.is_float[1])):
+            vals = np.ascontiguousarray(bits).view(np.float64)
+            cols[f] = vals if is_float else vals.astype(np.int64)
+            kinds[f] = FK_DOUBLE if is_float else FK_LONG
+        return ColumnBatch(int(keys.size), cols, tuple(kinds),
+                           self.dict if self.str_keys else None, ts, self._subtasks(keys), False)
+
+    def _on_watermark(self, wm: int) -> list:
+        return self.op.advance_watermark(wm)
+
+    def snapshot(self) -> dict:
+        snap = super().snapshot()
+        snap["ruleset"] = self.fn_spec
+        return snap
+
+    def restore(self, snap: dict) -> None:
+        spec = snap.get("ruleset")
+        if "fallback" not in snap and (spec is None or not _same_spec(spec, self.fn_spec)):
+            raise ValueError("checkpoint of a different rule-set function")
+        super().restore(snap)
+
+
 class _NoTimestamp(TypeError):
     """A record without an event timestamp (unsupported data; the host function's ValueError)."""
 

@@ -557,6 +557,114 @@ class CoProcessOp(KeyedProcessOp):
         super().restore(snap)
 
 
+class BroadcastProcessOp(KeyedProcessOp):
+    """CoBroadcastWithKeyedOperator / CoBroadcastWithNonKeyedOperator (Flink 1.8 broadcast
+    state). The input is the tagged union ``(side, value)``: side 0 is the first input, keyed here
+    by its own selector (`key_fn` takes the plain value; None: not keyed), side 1 the broadcast
+    input. Flink delivers a broadcast element to every parallel instance and every instance keeps
+    its own copy of the state, so there is one dict per descriptor and subtask:
+    process_broadcast_element is called once per subtask s = 0..P-1, in that order, with subtask
+    s's copy, and what it collects is stamped with s; apply_to_keyed_state visits only the keys
+    whose key group belongs to s. An element of the first input reads the copy of its key's
+    subtask (not keyed: of the record's own subtask). Keyed state, timers, on_timer, side outputs
+    and "nothing is late" are CoProcessOp's. One rank only: a replicating edge does not exist."""
+
+    name = "Co-Process-Broadcast"
+
+    def __init__(self, key_fn, fn, descriptors):
+        super().__init__(key_fn, fn)
+        self.descriptors = tuple(descriptors)
+
+    def open(self, ctx):
+        comm = getattr(ctx, "comm", None)
+        if comm is not None and comm.world > 1:
+            raise NotImplementedError("broadcast state runs on one rank only: the broadcast "
+                                      "input would need a replicating edge between the ranks")
+        if self.key_fn is not None:
+            super().open(ctx)
+        else:
+            Operator.open(self, ctx)
+            self.backend = None
+            self.timers = _Timers()  # stays empty: there is no timer service
+            _open_fn(self.fn, ctx)
+        self.copies = [{d.name: {} for d in self.descriptors} for _ in range(ctx.parallelism)]
+
+    def _base(self, ts, sub):
+        return (ts, self.copies[sub], self.side, lambda: self.wm, self.ctx.clock)
+
+    def _apply(self, sub: int, desc, fn) -> None:
+        """apply_to_keyed_state of subtask `sub`: every key of its key groups that has `desc`."""
+        table = self.backend._table(desc.name)
+        for key in list(dict.fromkeys(k for (k, _ns) in table)):
+            if self.subtask_of(key) != sub:
+                continue
+            self.backend.set_current_key(key)
+            self.backend.set_current_namespace(None)
+            fn(key, self.backend.get_state(desc))
+
+    def on_record(self, r):
+        side, value = r.value
+        ts = None if r.ts == LONG_MIN else r.ts
+        keyed = self.key_fn is not None
+        if side == 1:
+            out = []
+            for s in range(len(self.copies)):
+                col = F.Collector()
+                if keyed:
+                    c = F.KeyedBroadcastProcessFunction.Context(
+                        *self._base(ts, s), lambda desc, fn, s=s: self._apply(s, desc, fn))
+                else:
+                    c = F.BroadcastProcessFunction.Context(*self._base(ts, s))
+                self.fn.process_broadcast_element(value, c, col)
+                out.extend(Rec(v, r.ts, s) for v in col.items)
+            return out
+        col = F.Collector()
+        if keyed:
+            key = F.call_key(self.key_fn, value)
+            self.backend.set_current_key(key)
+            self.backend.set_current_namespace(None)
+            sub = self.subtask_of(key)
+            c = F.KeyedBroadcastProcessFunction.ReadOnlyContext(
+                *self._base(ts, sub), _TimerService(self, key), key)
+        else:
+            sub = r.subtask % len(self.copies)
+            c = F.BroadcastProcessFunction.ReadOnlyContext(*self._base(ts, sub))
+        self.fn.process_element(value, c, col)
+        return [Rec(v, r.ts, sub) for v in col.items]
+
+    def _fire(self, ts, key, domain) -> list:
+        col = F.Collector()
+        self.backend.set_current_key(key)
+        self.backend.set_current_namespace(None)
+        sub = self.subtask_of(key)
+        c = F.KeyedBroadcastProcessFunction.OnTimerContext(
+            *self._base(ts, sub), _TimerService(self, key), key, domain)
+        self.fn.on_timer(ts, c, col)
+        return [Rec(v, ts, sub) for v in col.items]
+
+    def snapshot(self):
+        import copy
+
+        snap = super().snapshot() if self.key_fn is not None else {"wm": self.wm}
+        snap["broadcast"] = copy.deepcopy(self.copies)
+        return snap
+
+    def restore(self, snap):
+        import copy
+
+        if self.key_fn is not None:
+            super().restore(snap)
+        else:
+            self.wm = snap.get("wm", LONG_MIN)
+        old = snap.get("broadcast") or [{}]
+        # another parallelism: subtask i takes copy i % len(copies) (every copy holds what a
+        # deterministic function made of the same broadcast elements)
+        for i, mine in enumerate(self.copies):
+            for name, entries in copy.deepcopy(old[i % len(old)]).items():
+                if name in mine:
+                    mine[name] = entries
+
+
 def _sat_add(a: int, b: int) -> int:
     return max(LONG_MIN, min(LONG_MAX, a + b))
 
