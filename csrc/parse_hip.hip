@@ -111,6 +111,7 @@ __device__ __forceinline__ uint8_t parse_one_line(Text text, const int64_t* __re
                                                   uint8_t* __restrict__ status) {
   const int64_t a = starts[li];
   int64_t b = li + 1 < nlines ? starts[li + 1] - 1 : text_len;  // exclusive end (drop '\n')
+  if (b > a && text[b - 1] == '\n') --b;  // the last line of a batch ending in '\n'
   if (b > a && text[b - 1] == '\r') --b;  // SocketTextStreamFunction strips a trailing '\r'
   // Field boundaries of the requested indices (Java String.split semantics: trailing empty
   // fields are dropped, so an index at or past them is out of bounds). Positions are kept per

@@ -132,6 +132,8 @@ def _host_patch(m, data: bytes, starts: np.ndarray, bad: np.ndarray, spec, sep, 
     lines = []
     for i in bad.tolist():
         line = data[starts[i]:ends[i]]
+        if line.endswith(b"\n"):  # the last line of a batch ending in '\n' (as the kernel cuts it)
+            line = line[:-1]
         if line.endswith(b"\r"):
             line = line[:-1]
         lines.append(line)
@@ -143,12 +145,15 @@ def _host_patch(m, data: bytes, starts: np.ndarray, bad: np.ndarray, spec, sep, 
         raise ParseError(f"line {int(bad[err_idx]) + 1}: {err}")
     dev = cols.device
     idx = torch.from_numpy(bad.astype(np.int64)).to(dev)
-    strings = d.strings()
-    for f, (_, kind) in enumerate(spec):
+    bsep = sep.encode()
+    for f, (fi, kind) in enumerate(spec):
         vals = res_cols[f]
         if kind == FK_STR:
-            keys = np.array([fnv1a64(strings[i].encode()) for i in vals.tolist()], dtype=np.int64)
-            hs = np.array([m.java_string_hash(strings[i]) for i in vals.tolist()], dtype=np.int32)
+            # The field's bytes as they stand in the line (parse_lines found the field present):
+            # the key hashes the bytes, so invalid UTF-8 must not pass through a str.
+            fields = [ln.split(bsep)[fi] for ln in lines]
+            keys = np.array([fnv1a64(b) for b in fields], dtype=np.int64)
+            hs = np.array([m.java_string_hash(b) for b in fields], dtype=np.int32)
             jh[f * n + idx] = torch.from_numpy(hs).to(dev)
             vals = keys
         elif kind == FK_DOUBLE:
