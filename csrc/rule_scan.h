@@ -1,7 +1,8 @@
 // mxstream — what the keyed rules' device code shares: the host helpers of csrc/mxs_hip_util.h
-// for their four units (csrc/timeout_hip.hip, sustain_hip.hip, burst_hip.hip, reorder_hip.hip),
-// and for the rules that scan a batch sorted by key (sustain_scan_kernel, burst_scan_kernel) the
-// scan frame: who owns a key's run, the append of a transition, and when a wave walks on.
+// for their five units (csrc/timeout_hip.hip, sustain_hip.hip, burst_hip.hip, reorder_hip.hip,
+// fsm_hip.hip), and for the rules that scan a batch sorted by key (sustain_scan_kernel,
+// burst_scan_kernel, fsm_scan_kernel) the scan frame: who owns a key's run, the append of a
+// transition, and when a wave walks on.
 // Included from .hip files only.
 //
 // The frame. The batch arrives stably sorted by key (`skeys`, with `perm` = the arrival index of
@@ -14,7 +15,8 @@
 // touch it. Transitions are appended with one reservation per wave and chunk that has any
 // (ballot / popcount), each tagged ``arrival index << 1 | code``; sustain_gather_kernel
 // (csrc/sustain_hip.hip), the family's gather, turns the rows sorted by tag into the five
-// output columns.
+// output columns. The state machines' rows carry 8 bits of code: rule_row_append and a gather of
+// their own (csrc/fsm_hip.hip).
 //
 // A kernel's loops around the frame:
 //   for (base = the wave's first row; base < n; base += the grid's rows)   // the wave's chunks
@@ -112,6 +114,26 @@ __device__ __forceinline__ void rule_edge_append(bool fire, bool resolve, int64_
     if (q < n) {  // at most one row per element: always true
       out_tag[q] = (src << 1) | (fire ? 1 : 0);
       out_since[q] = fire ? s1 : s0;
+    }
+  }
+}
+
+// The same append for a rule whose rows carry a wider code (fsm_scan_kernel: 8 bits): the lane's
+// own `tag` = ``arrival << bits | code`` and `since`. `emit` is false in a lane that is not `ok`.
+// All 64 lanes call it.
+__device__ __forceinline__ void rule_row_append(bool emit, int64_t tag, int64_t since, int64_t n,
+                                                int64_t* __restrict__ out_tag,
+                                                int64_t* __restrict__ out_since,
+                                                uint32_t* __restrict__ out_n, int lane) {
+  const unsigned long long m = __ballot(emit);
+  uint32_t wb = 0;
+  if (lane == 0 && m) wb = atomicAdd(out_n, (uint32_t)__popcll(m));
+  wb = __shfl(wb, 0);
+  if (emit) {
+    const int64_t q = (int64_t)wb + __popcll(m & ((1ull << lane) - 1ull));
+    if (q < n) {  // at most one row per element: always true
+      out_tag[q] = tag;
+      out_since[q] = since;
     }
   }
 }

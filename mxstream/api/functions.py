@@ -844,6 +844,122 @@ class BurstAlert(KeyedProcessFunction):
             self._state.update((recent, since, firing))
 
 
+class StateMachineAlert(KeyedProcessFunction):
+    """A finite state machine per key, stepped by every element (Flink's StateMachineExample; a
+    warning / critical / ok severity reported once per change; hysteresis; "three breaches in a
+    row"): ``value[field]`` falls into class ``c`` = the number of `bounds` ``b`` with
+    ``value >= b``, and the key moves ``to = table[from][c]``. A key enters `initial` at its
+    first element, which then steps it like any other. Every reported pair ``(from, to)``
+    collects ``Tuple5(key, from, to, since, value[field])``, `since` being the timestamp at which
+    the key entered `from` (``ts - since`` is how long it stayed). Elements are taken in arrival
+    order, output records carry their element's timestamp, and there are no timers. Values are
+    int or float (not bool) and compare as Java compares doubles: a NaN is class 0 and
+    ``-0.0 >= 0.0`` holds. `bounds` holds 1 to 15 finite ints or floats, strictly ascending;
+    `table` has one row per state and one entry per class (``len(bounds) + 1``), each a state;
+    `report` is ``"change"`` (every pair with ``from != to``) or an iterable of ``(from, to)``
+    pairs, self-loops allowed, possibly empty. An integer event type ``e`` in ``[0, C)`` is its
+    own class with ``bounds = [1, 2, .., C - 1]``. On above 90, off only below 80:
+
+        samples.key_by(0).process(StateMachineAlert(2, [80.0, 90.0], [[0, 0, 1], [0, 1, 1]]))
+
+    The planner runs exactly this class (not a subclass) with a positional key and at most 16
+    states on the device operator (runtime/fsm_operator.py); these methods are the exact host
+    implementation used otherwise."""
+
+    def __init__(self, field: int, bounds, table, initial: int = 0, report="change"):
+        import math
+
+        def is_int(x):
+            return isinstance(x, int) and not isinstance(x, bool)
+
+        if not is_int(field) or field < 0:
+            raise ValueError(f"StateMachineAlert: field is a non-negative int, got {field!r}")
+        try:
+            bounds = tuple(bounds)
+        except TypeError:
+            raise TypeError(f"StateMachineAlert: bounds is a sequence of numbers, got {bounds!r}") \
+                from None
+        for b in bounds:
+            self._number(b, "a bound")
+        if not 1 <= len(bounds) <= 15:
+            raise ValueError(f"StateMachineAlert: 1 to 15 bounds, got {len(bounds)}")
+        try:
+            cuts = tuple(float(b) for b in bounds)
+        except OverflowError:
+            raise ValueError("StateMachineAlert: the bounds must be finite") from None
+        if not all(math.isfinite(c) for c in cuts) or any(a >= b for a, b in zip(cuts, cuts[1:])):
+            raise ValueError("StateMachineAlert: the bounds must be finite and strictly "
+                             f"ascending, got {bounds!r}")
+        try:
+            table = tuple(tuple(row) for row in table)
+        except TypeError:
+            raise TypeError("StateMachineAlert: table is a sequence of rows of states, got "
+                            f"{table!r}") from None
+        states, classes = len(table), len(cuts) + 1
+        if states < 1:
+            raise ValueError("StateMachineAlert: the table needs at least one state")
+        for s, row in enumerate(table):
+            if len(row) != classes:
+                raise ValueError(f"StateMachineAlert: table[{s}] needs one entry per class "
+                                 f"({classes}), got {len(row)}")
+            for to in row:
+                if not is_int(to) or not 0 <= to < states:
+                    raise ValueError(f"StateMachineAlert: table[{s}] holds {to!r}, no state in "
+                                     f"[0, {states})")
+        if not is_int(initial) or not 0 <= initial < states:
+            raise ValueError(f"StateMachineAlert: initial is a state in [0, {states}), got "
+                             f"{initial!r}")
+        if isinstance(report, str):
+            if report != "change":
+                raise ValueError("StateMachineAlert: report is 'change' or an iterable of "
+                                 f"(from, to) pairs, got {report!r}")
+            pairs = {(a, b) for a in range(states) for b in range(states) if a != b}
+        else:
+            try:
+                pairs = {tuple(p) for p in report}
+            except TypeError:
+                raise TypeError("StateMachineAlert: report is 'change' or an iterable of "
+                                f"(from, to) pairs, got {report!r}") from None
+            for p in pairs:
+                if len(p) != 2 or not all(is_int(x) and 0 <= x < states for x in p):
+                    raise ValueError(f"StateMachineAlert: the reported pair {p!r} is no pair of "
+                                     f"states in [0, {states})")
+        self.field, self.bounds, self.table, self.initial = field, cuts, table, initial
+        self.report = tuple(sorted(pairs))
+        self._reported = frozenset(pairs)
+        # the bounds as the doubles they are compared as: 80 and 80.0 are one rule
+        self.native = ("state_machine", field, cuts, table, initial, self.report)
+
+    @staticmethod
+    def _number(x, what: str):
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise TypeError(f"StateMachineAlert: {what} must be an int or a float, got {x!r}")
+        return x
+
+    def open(self, parameters=None):
+        from .state import ValueStateDescriptor
+
+        self._state = self.get_runtime_context().get_state(
+            ValueStateDescriptor("state-machine-alert"))
+
+    def process_element(self, value, ctx, out):
+        from .tuples import Tuple5
+
+        ts = ctx.timestamp()
+        if ts is None:
+            raise ValueError("StateMachineAlert: a record without an event timestamp")
+        v = self._number(value[self.field], "the element's value")
+        since, state = self._state.value() or (ts, self.initial)
+        # Python compares an int with a float exactly; Java compares the two doubles
+        x = float(v)
+        to = self.table[state][sum(x >= b for b in self.bounds)]
+        if (state, to) in self._reported:
+            out.collect(Tuple5(ctx.get_current_key(), state, to, since, v))
+        if to != state:
+            since = ts
+        self._state.update((since, to))
+
+
 class _NoTimerService:
     """What a function wrapped by EventTimeOrdered finds in place of the timer service."""
 
@@ -878,8 +994,9 @@ class EventTimeOrdered(KeyedProcessFunction):
 
         samples.key_by(0).process(EventTimeOrdered(SustainedAlert(2, ">", 90.0, Time.minutes(5))))
 
-    The planner runs exactly this class around exactly a ``SustainedAlert`` or a ``BurstAlert``
-    (``times <= 16``) with a positional key on the device reorder buffer
+    The planner runs exactly this class around exactly a ``SustainedAlert``, a ``BurstAlert``
+    (``times <= 16``) or a ``StateMachineAlert`` (at most 16 states) with a positional key on
+    the device reorder buffer
     (runtime/reorder_operator.py) in front of the rule's device operator; these methods are the
     exact host implementation used otherwise."""
 

@@ -27,8 +27,9 @@ NativeRuleSetOp (``_lower_broadcast_connect``); every other broadcast function k
 BroadcastProcessOp.
 ``key_by(p).process(CountWithTimeout(..))`` is lowered onto NativeTimeoutOp and
 ``key_by(p).process(SustainedAlert(..))`` onto NativeSustainOp and
-``key_by(p).process(BurstAlert(..))`` with ``times <= 16`` onto NativeBurstOp
-(``_lower_keyed_process``), each of the last two also under ``EventTimeOrdered(..)``, with the
+``key_by(p).process(BurstAlert(..))`` with ``times <= 16`` onto NativeBurstOp and
+``key_by(p).process(StateMachineAlert(..))`` with at most 16 states onto NativeStateMachineOp
+(``_lower_keyed_process``), each of the last three also under ``EventTimeOrdered(..)``, with the
 device reorder buffer in front; every other keyed process function keeps KeyedProcessOp.
 
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
@@ -1006,17 +1007,21 @@ def _lower_broadcast_connect(env, t, meta) -> None:
 
 def _lower_keyed_process(env, t, meta) -> None:
     """``stream.key_by(p).process(fn)`` -> NativeTimeoutOp when `fn` is exactly a
-    ``CountWithTimeout``, -> NativeSustainOp when it is exactly a ``SustainedAlert`` and ->
+    ``CountWithTimeout``, -> NativeSustainOp when it is exactly a ``SustainedAlert``, ->
     NativeBurstOp when it is exactly a ``BurstAlert`` with ``times <= 16``, the width of the
-    engine's per-key ring (not a subclass, whose methods may differ), the key is a field position
-    and one rank runs the job. Every other keyed process function, a ``BurstAlert`` with more
-    `times`, key selectors and several ranks keep the host KeyedProcessOp.
+    engine's per-key ring, and -> NativeStateMachineOp when it is exactly a
+    ``StateMachineAlert`` with at most 16 states and 16 classes, what one packed function holds
+    (not a subclass, whose methods may differ), the key is a field position and one rank runs
+    the job. Every other keyed process function, a ``BurstAlert`` with more `times`, a
+    ``StateMachineAlert`` with a larger table, key selectors and several ranks keep the host
+    KeyedProcessOp.
 
-    ``EventTimeOrdered(fn)`` (exactly that class) around exactly a ``SustainedAlert`` or a
-    ``BurstAlert`` lowers, under the same conditions, onto the same operators with
-    ``ordered=True``: the device reorder buffer in front of the rule."""
-    from ..ops.kernels import BURST_MAX_TIMES
-    from ..runtime.native_ops import NativeBurstOp, NativeSustainOp, NativeTimeoutOp
+    ``EventTimeOrdered(fn)`` (exactly that class) around exactly a ``SustainedAlert``, a
+    ``BurstAlert`` or a ``StateMachineAlert`` lowers, under the same conditions, onto the same
+    operators with ``ordered=True``: the device reorder buffer in front of the rule."""
+    from ..ops.kernels import BURST_MAX_TIMES, FSM_MAX_CLASSES, FSM_MAX_STATES
+    from ..runtime.native_ops import (NativeBurstOp, NativeStateMachineOp, NativeSustainOp,
+                                      NativeTimeoutOp)
     from . import functions as F
 
     fn, kp = meta["fn"], meta["key_pos"]
@@ -1024,16 +1029,20 @@ def _lower_keyed_process(env, t, meta) -> None:
     world = comm.world if comm is not None else getattr(env, "world", 1)
     kw = {}
     if type(fn) is F.EventTimeOrdered:
-        # the device reorder buffer in front of the two rules; any other wrapped function keeps
-        # the host wrapper
+        # the device reorder buffer in front of the rules; any other wrapped function keeps the
+        # host wrapper
         fn, kw = fn.fn, {"ordered": True}
-        if type(fn) not in (F.SustainedAlert, F.BurstAlert):
+        if type(fn) not in (F.SustainedAlert, F.BurstAlert, F.StateMachineAlert):
             return
     native = {F.CountWithTimeout: NativeTimeoutOp, F.SustainedAlert: NativeSustainOp,
-              F.BurstAlert: NativeBurstOp}.get(type(fn))
+              F.BurstAlert: NativeBurstOp,
+              F.StateMachineAlert: NativeStateMachineOp}.get(type(fn))
     if native is None or kp is None or world > 1:
         return
     if native is NativeBurstOp and fn.times > BURST_MAX_TIMES:
+        return
+    if native is NativeStateMachineOp and (len(fn.table) > FSM_MAX_STATES
+                                           or len(fn.bounds) + 1 > FSM_MAX_CLASSES):
         return
     fallback = t.factory
     device = env.config.device

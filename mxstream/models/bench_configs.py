@@ -1566,6 +1566,103 @@ def config19(steps: int, warmup: int, batch: int | None = None, keys: int = 1_00
             "device": str(dev)}
 
 
+def config21(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             states: int = 3, zipf: float = 0.0, device: str = "cuda") -> dict:
+    """Keyed state machines at scale (``samples.key_by(0).process(StateMachineAlert(2, bounds,
+    table))``) on config 17's data: `batch` device-generated samples per 1 s step (gen_events,
+    uniform or zipf keys) feed KeyedStateMachineOperator directly; a key breaches for 10
+    consecutive steps out of every 1000, at a phase of its own, with values in 91..99, all
+    others in 0..89. `states` = 3 is a severity with hysteresis over the bounds (90, 95): ok /
+    warning / critical, critical held until the value falls below 90, every change reported;
+    any other `states` (2 .. 16) is a saturating counter of breaches in a row over the bound
+    90, reported when it saturates and when a saturated key falls back -- 16 is the
+    composition-bound case, every function 16 nibbles wide. The rows leave the device as five
+    int64 columns (key id, from << 4 | to, since, value, ts) in arrival order.
+
+    Timed per step, each behind a device synchronise, alternating in the same call on the same
+    batch: the state-machine step and config 17's native step (KeyedSustainOperator, ``for_`` =
+    3 s). Both sort by key, scan, read the count back and sort their rows by arrival; the
+    difference is the scan and one more radix digit of the rows' tags. The ratio is reported,
+    not gated. Outside both windows the C++ twin runs every step on host copies: every step's
+    row count, the first three steps' rows and the final table must equal the device's. The
+    sample generation is outside the windows too."""
+    from ..runtime.fsm_operator import KeyedStateMachineOperator
+    from ..runtime.sustain_operator import KeyedSustainOperator
+
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    if states == 3:
+        bounds, table, report = [90, 95], [[0, 1, 2], [0, 1, 2], [0, 2, 2]], "change"
+    elif 2 <= states <= 16:
+        top = states - 1
+        bounds, table = [90], [[0, min(s + 1, top)] for s in range(states)]
+        report = [(top - 1, top), (top, 0)]
+    else:
+        raise ValueError("config 21: --states lies in [2, 16]")
+    op = KeyedStateMachineOperator(bounds, table, 0, report, device=dev,
+                                   dense_limit=max(keys, 1 << 26), capacity=keys)
+    sustain = KeyedSustainOperator(">", 90, 3_000, device=dev, dense_limit=max(keys, 1 << 26),
+                                   capacity=keys)
+    twin = K.fsm_table(keys, "cpu")
+    rule = dict(cuts=op.cuts, cols=op.cols, report=op.masks, states=op.states,
+                classes=op.classes, initial=op.initial)
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    sk, st, sv = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(3))
+    state = {"i": 0}
+    fsm_ms: list[float] = []
+    sustain_ms: list[float] = []
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, sv, seed=17, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=0,
+                     val_span=100, zipf=zipf)
+        breach = (sk * 2_654_435_761 + i) % 1_000 < 10
+        sv.copy_(torch.where(breach, 91 + sv % 9, sv % 90))
+        _sync(dev)
+        t_in = time.perf_counter()
+        out = op.process(sk, sv, st, is_float=False)
+        _sync(dev)
+        fsm_ms.append((time.perf_counter() - t_in) * 1e3)
+        t_in = time.perf_counter()
+        ref = sustain.process(sk, sv, st, is_float=False)
+        _sync(dev)
+        sustain_ms.append((time.perf_counter() - t_in) * 1e3)
+        want = K.fsm_update(twin, sk.cpu(), sv.cpu(), st.cpu(), kind=K.SUSTAIN_LONG, **rule)
+        rows = int(out[0][0].numel()) if out else 0
+        if rows != int(want[0].numel()) or (i < 3 and out and not all(
+                torch.equal(a.cpu(), b) for a, b in zip(out[0], want))):
+            raise RuntimeError("config 21: the native rows and the twin's differ")
+        state["i"] = i + 1
+        return rows, int(ref[0][0].numel()) if ref else 0
+
+    for _ in range(warmup):
+        step()
+    fsm_ms.clear()
+    sustain_ms.clear()
+    rows = sustain_rows = 0
+    for _ in range(steps):
+        r, s = step()
+        rows, sustain_rows = rows + r, sustain_rows + s
+    if not torch.equal(op.state[:keys].cpu(), twin):
+        raise RuntimeError("config 21: the native table and the twin's differ")
+    seen = twin[:, 0] != K.FSM_NONE
+    nat, ref = _spread(fsm_ms), _spread(sustain_ms)
+    return {"config": 21, "metric": "events/sec (keyed state machines: packed-function scan)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "native_ms": nat, "sustain_ms": ref,
+            "sustain_events_per_s": batch / ref["median"] * 1e3,
+            "fsm_over_sustain_time": nat["median"] / ref["median"],
+            "rows": rows, "rows_per_step": rows // max(1, steps),
+            "sustain_rows_per_step": sustain_rows // max(1, steps),
+            "keys_seen": int(seen.sum()),
+            "keys_per_state": torch.bincount(twin[seen, 1], minlength=states).tolist(),
+            "states": states, "classes": op.classes, "keys": keys, "samples_per_step": batch,
+            "zipf": zipf, "table_rows": op.cap, "steps": steps, "warmup": warmup,
+            "device": str(dev)}
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1848,7 +1945,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1883,6 +1980,10 @@ def main(argv=None) -> int:
                          "span, and the watermark runs this far behind (0: an in-order stream)")
     ap.add_argument("--rules", type=int, default=8,
                     help="config 20: rules in force (1 .. 64); rule r is > 9900 + 10 r")
+    ap.add_argument("--states", type=int, default=3,
+                    help="config 21: 3 is the severity with hysteresis; any other count in "
+                         "[2, 16] a saturating counter of breaches in a row (16: the widest "
+                         "packed function)")
     ap.add_argument("--dense", action="store_true",
                     help="config 20: every sample breaks every rule (the expansion-bound case)")
     ap.add_argument("--steps", type=int, default=20)
@@ -1979,6 +2080,9 @@ def main(argv=None) -> int:
     elif a.config == 20:
         r = config20(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, rules=a.rules,
                      dense=a.dense, device=a.device)
+    elif a.config == 21:
+        r = config21(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, states=a.states,
+                     zipf=a.zipf, device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

@@ -1302,12 +1302,14 @@ def sustain_table(cap: int, device) -> torch.Tensor:
     return state
 
 
-def _rule_update(row: torch.Tensor, keys, vals, ts, bounds, name: str, twin, scan):
+def _rule_update(row: torch.Tensor, keys, vals, ts, bounds, name: str, twin, scan,
+                 code_bits: int = 1, gather: str = "gpu_sustain_gather"):
     """What the rules over a batch sorted by key share once their parameters are checked (`row`
     is the rule's [cap, 2] table, `name` the caller's for messages): the bounds, then on the CPU
     ``twin(*five output pointers)`` -> rows, else the sort by key, ``scan(skeys, perm, tags,
     since, count, stream)`` (pointers), the count's readback, the sort by arrival index and the
-    family's gather. Five columns in arrival order."""
+    gather. Five columns in arrival order. A row's tag is ``arrival << code_bits | code``;
+    `gather` names the native function that takes such tags apart (the family's, for one bit)."""
     dev = row.device
     cap, n = row.shape[0], keys.numel()
     out = torch.empty((5, n), dtype=torch.int64, device=dev)
@@ -1338,12 +1340,12 @@ def _rule_update(row: torch.Tensor, keys, vals, ts, bounds, name: str, twin, sca
         raise RuntimeError(f"{name}: more transitions than rows")
     if rows == 0:
         return tuple(out[c, :0] for c in range(5))
-    # Arrival order: the tags are ``arrival << 1 | code``, one per element at most.
+    # Arrival order: the tags are ``arrival << code_bits | code``, one per element at most.
     tags, since = scratch[0, :rows], scratch[1, :rows]
     if rows > 1:
-        tags, since = sort_pairs(tags, since, bits=(n - 1).bit_length() + 1)
-    load().gpu_sustain_gather(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
-                              *(_p(out[c]) for c in range(5)), st)
+        tags, since = sort_pairs(tags, since, bits=(n - 1).bit_length() + code_bits)
+    getattr(load(), gather)(_p(tags), _p(since), rows, _p(keys), _p(vals), _p(ts), n,
+                            *(_p(out[c]) for c in range(5)), st)
     return tuple(out[c, :rows] for c in range(5))
 
 
@@ -1437,6 +1439,117 @@ def burst_update(ring: torch.Tensor, row: torch.Tensor, keys: torch.Tensor, vals
         lambda *outs: load().cpu_burst_update(_p(keys), _p(vals), _p(ts), *rule, *outs),
         lambda skeys, perm, *outs: load().gpu_burst_scan(skeys, perm, _p(vals), _p(ts), *rule,
                                                          *outs))
+
+
+# ---- keyed state machines (csrc/mxs_fsm.h) ------------------------------------------------------
+
+FSM_NONE = I64_MIN            # `since` of a key that was never seen
+FSM_MAX_STATES = FSM_MAX_CLASSES = 16   # a function S -> S packs into one 64-bit word
+FSM_TAG_BITS = 8              # a row's tag = arrival << 8 | from << 4 | to
+
+
+def fsm_table(cap: int, device) -> torch.Tensor:
+    """Fresh state for `cap` key ids: int64[cap, 2], every row (FSM_NONE, 0)."""
+    if cap < 1:
+        raise ValueError("fsm: cap must be >= 1")
+    state = torch.zeros((cap, 2), dtype=torch.int64, device=device)
+    state[:, 0] = FSM_NONE
+    return state
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def fsm_pack(bounds, table, report):
+    """A state machine's parameters as the engine takes them: (cuts, cols, masks). `bounds`:
+    classes - 1 finite numbers, strictly ascending as doubles; `table`: states rows of classes
+    ints in [0, states); `report`: (from, to) pairs. cuts: the bounds as floats; cols[c]: the
+    table's column c as a function, nibble s = table[s][c]; masks[from]: bit `to` set for a
+    reported pair. At most 16 states and 16 classes."""
+    table = [list(r) for r in table]
+    states = len(table)
+    if not 1 <= states <= FSM_MAX_STATES:
+        raise ValueError(f"fsm: 1 to {FSM_MAX_STATES} states, got {states}")
+    classes = len(table[0])
+    if not 1 <= classes <= FSM_MAX_CLASSES:
+        raise ValueError(f"fsm: 1 to {FSM_MAX_CLASSES} classes, got {classes}")
+    bounds = list(bounds)
+    if len(bounds) != classes - 1:
+        raise ValueError("fsm: the table has one more column than there are bounds")
+    if any(isinstance(b, bool) or not isinstance(b, (int, float)) for b in bounds):
+        raise TypeError("fsm: a bound must be an int or a float")
+    cuts = tuple(float(b) for b in bounds)
+    if any(c != c or c in (float("inf"), float("-inf")) for c in cuts) \
+            or any(a >= b for a, b in zip(cuts, cuts[1:])):
+        raise ValueError("fsm: the bounds must be finite and strictly ascending")
+    cols = [0] * classes
+    for s, row in enumerate(table):
+        if len(row) != classes:
+            raise ValueError("fsm: every table row has one entry per class")
+        for c, to in enumerate(row):
+            if not _is_int(to) or not 0 <= to < states:
+                raise ValueError(f"fsm: table[{s}][{c}] = {to!r} is no state in [0, {states})")
+            cols[c] |= to << (4 * s)
+    masks = [0] * states
+    for pair in report:
+        a, b = pair
+        if not _is_int(a) or not _is_int(b) or not (0 <= a < states and 0 <= b < states):
+            raise ValueError(f"fsm: the reported pair {pair!r} is no pair of states")
+        masks[a] |= 1 << b
+    return cuts, tuple(cols), tuple(masks)
+
+
+def fsm_update(state: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, ts: torch.Tensor,
+               *, kind: int, cuts, cols, report, states: int, classes: int, initial: int,
+               bounds: tuple | None = None):
+    """A batch of elements in arrival order (key ids, value bits of `kind`, timestamps) against
+    a state machine per key (`cuts`, `cols`, `report` as fsm_pack gives them, `report` being its
+    masks; `states` and `classes` their lengths): an element's class is the number of cuts its
+    value reaches, ``to = table[from][class]``, and a reported (from, to) is a row. The table is
+    updated and the rows come back in arrival order as five int64 columns (key id,
+    from << 4 | to, since, value bits, ts), `since` being the timestamp at which the key entered
+    `from`. Every key must lie in [0, cap) and every timestamp strictly inside (-2**62, 2**62)
+    (`bounds` = (largest key, smallest and largest timestamp) when the caller has read them,
+    else one readback). GPU: stable radix sort by key, one segmented wave scan of the packed
+    functions, the rows' count read back, a radix sort of the rows by arrival index; a one-row
+    batch skips the first sort."""
+    dev = state.device
+    try:
+        cap = _lookup_table(state)
+    except ValueError:
+        raise ValueError("fsm_update: the table must be a contiguous, 16-byte aligned int64 "
+                         "[cap, 2] tensor with cap >= 1") from None
+    n = _lookup_cols((keys, vals, ts), ("keys", "vals", "ts"), dev)
+    if kind not in (SUSTAIN_LONG, SUSTAIN_DOUBLE):
+        raise ValueError("fsm_update: kind must be SUSTAIN_LONG or SUSTAIN_DOUBLE")
+    if not _is_int(states) or not 1 <= states <= FSM_MAX_STATES:
+        raise ValueError(f"fsm_update: states must be an int in [1, {FSM_MAX_STATES}]")
+    if not _is_int(classes) or not 1 <= classes <= FSM_MAX_CLASSES:
+        raise ValueError(f"fsm_update: classes must be an int in [1, {FSM_MAX_CLASSES}]")
+    cuts, cols, report = tuple(cuts), tuple(cols), tuple(report)
+    if len(cuts) != classes - 1 or len(cols) != classes or len(report) != states:
+        raise ValueError("fsm_update: classes - 1 cuts, classes columns and states masks expected")
+    if not _is_int(initial) or not 0 <= initial < states:
+        raise ValueError(f"fsm_update: initial must be a state in [0, {states})")
+    if any(not isinstance(c, float) or c != c or abs(c) == float("inf") for c in cuts) \
+            or any(a >= b for a, b in zip(cuts, cuts[1:])):
+        raise ValueError("fsm_update: the cuts must be finite floats, strictly ascending")
+    for c in cols:
+        if not _is_int(c) or not 0 <= c < 1 << 64 or c >> (4 * states) \
+                or any((c >> (4 * s)) & 15 >= states for s in range(states)):
+            raise ValueError(f"fsm_update: a table entry is no state in [0, {states})")
+    if any(not _is_int(m) or not 0 <= m < 1 << states for m in report):
+        raise ValueError("fsm_update: a reported pair is no pair of states")
+    if n >= 1 << 31:
+        raise ValueError("fsm_update: at most 2**31 - 1 rows per batch")
+    rule = (n, cuts, cols, report, initial, kind, _p(state), cap)
+    return _rule_update(
+        state, keys, vals, ts, bounds, "fsm_update",
+        lambda *outs: load().cpu_fsm_update(_p(keys), _p(vals), _p(ts), *rule, *outs),
+        lambda skeys, perm, *outs: load().gpu_fsm_scan(skeys, perm, _p(vals), _p(ts), *rule,
+                                                       *outs),
+        code_bits=FSM_TAG_BITS, gather="gpu_fsm_gather")
 
 
 # ---- event-time reorder buffer (csrc/mxs_reorder.h) ---------------------------------------------

@@ -2732,13 +2732,12 @@ class NativeSustainOp(_NativeKeyedRuleOp):
         self.fn_spec = tuple(fn.native)
         self.ordered = bool(ordered)
         self.buf = None   # the EventOrderBuffer of an ordered operator, from its first batch on
-        self.when, self.threshold = fn.when, fn.threshold
         self._rule(fn)
         self.key_pos, self.val_pos = key_pos, fn.field
         self.dense_limit = int(dense_limit)
 
     def _rule(self, fn) -> None:
-        self.for_ms = fn.for_ms
+        self.when, self.threshold, self.for_ms = fn.when, fn.threshold, fn.for_ms
 
     def _build(self) -> None:
         from .sustain_operator import KeyedSustainOperator
@@ -2821,12 +2820,15 @@ class NativeSustainOp(_NativeKeyedRuleOp):
         for cols in self.op.process(keys, bits, ts, is_float=is_float):
             key, code, since, val, t = (c.cpu().numpy() for c in cols)
             vals = np.ascontiguousarray(val).view(np.float64) if is_float else val
-            out.append(ColumnBatch(int(key.size), [key, code, since, vals],
-                                   (FK_STR if self.str_keys else FK_LONG, FK_LONG, FK_LONG,
-                                    FK_DOUBLE if is_float else FK_LONG),
-                                   self.dict if self.str_keys else None, t,
-                                   self._subtasks(key), False))
+            out.append(self._row_batch(key, code, since, vals, t, is_float))
         return out
+
+    def _row_batch(self, key, code, since, vals, t, is_float: bool) -> ColumnBatch:
+        """The engine's rows (host arrays) as the function's output tuples."""
+        return ColumnBatch(int(key.size), [key, code, since, vals],
+                           (FK_STR if self.str_keys else FK_LONG, FK_LONG, FK_LONG,
+                            FK_DOUBLE if is_float else FK_LONG),
+                           self.dict if self.str_keys else None, t, self._subtasks(key), False)
 
     def _has_state(self) -> bool:
         return self.op is not None or self.buf is not None
@@ -2884,6 +2886,7 @@ class NativeBurstOp(NativeSustainOp):
     fn_name, snap_key, snap_what = "BurstAlert", "burst", "burst-alert"
 
     def _rule(self, fn) -> None:
+        self.when, self.threshold = fn.when, fn.threshold
         self.times, self.within_ms = fn.times, fn.within_ms
 
     def _build(self) -> None:
@@ -2892,6 +2895,35 @@ class NativeBurstOp(NativeSustainOp):
         self.op = KeyedBurstOperator(self.when, self.threshold, self.times, self.within_ms,
                                      device=torch.device(self.device),
                                      dense_limit=self.dense_limit)
+
+
+class NativeStateMachineOp(NativeSustainOp):
+    """``stream.key_by(p).process(StateMachineAlert(field, bounds, table, initial, report))`` on
+    the device operator (runtime/fsm_operator.py; planner._lower_keyed_process). Inputs,
+    buffering, event-time order, what counts as unsupported data and what becomes of it are
+    NativeSustainOp's; the engine, the checkpoint's key ("state_machine") and the output differ:
+    one host ColumnBatch ``(key, from, to, since, value)``, the engine's code column
+    ``from << 4 | to`` split in two."""
+
+    name = "KeyedProcess(native state machine)"
+    fn_name, snap_key, snap_what = "StateMachineAlert", "state_machine", "state-machine"
+
+    def _rule(self, fn) -> None:
+        self.bounds, self.table = fn.bounds, fn.table
+        self.initial, self.report = fn.initial, fn.report
+
+    def _build(self) -> None:
+        from .fsm_operator import KeyedStateMachineOperator
+
+        self.op = KeyedStateMachineOperator(self.bounds, self.table, self.initial, self.report,
+                                            device=torch.device(self.device),
+                                            dense_limit=self.dense_limit)
+
+    def _row_batch(self, key, code, since, vals, t, is_float: bool) -> ColumnBatch:
+        return ColumnBatch(int(key.size), [key, code >> 4, code & 15, since, vals],
+                           (FK_STR if self.str_keys else FK_LONG, FK_LONG, FK_LONG, FK_LONG,
+                            FK_DOUBLE if is_float else FK_LONG),
+                           self.dict if self.str_keys else None, t, self._subtasks(key), False)
 
 
 def _same_spec(a, b) -> bool:
