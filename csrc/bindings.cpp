@@ -1358,6 +1358,7 @@ PYBIND11_MODULE(_mxs_native, m) {
   bind_sustain(m);
   bind_burst(m);
   bind_fsm(m);
+  bind_rate(m);
   bind_reorder(m);
   bind_ruleset(m);
   bind_window_tier(m);

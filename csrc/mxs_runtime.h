@@ -18,6 +18,7 @@ void bind_timeout(pybind11::module_& m);
 void bind_sustain(pybind11::module_& m);
 void bind_burst(pybind11::module_& m);
 void bind_fsm(pybind11::module_& m);
+void bind_rate(pybind11::module_& m);
 void bind_reorder(pybind11::module_& m);
 void bind_ruleset(pybind11::module_& m);
 void bind_window_tier(pybind11::module_& m);

@@ -1,8 +1,10 @@
 // mxstream — what the keyed rules' device code shares: the host helpers of csrc/mxs_hip_util.h
-// for their five units (csrc/timeout_hip.hip, sustain_hip.hip, burst_hip.hip, reorder_hip.hip,
-// fsm_hip.hip), and for the rules that scan a batch sorted by key (sustain_scan_kernel,
-// burst_scan_kernel, fsm_scan_kernel) the scan frame: who owns a key's run, the append of a
-// transition, and when a wave walks on.
+// for their six units (csrc/timeout_hip.hip, sustain_hip.hip, burst_hip.hip, reorder_hip.hip,
+// fsm_hip.hip, rate_hip.hip), and for the rules that scan a batch sorted by key
+// (sustain_scan_kernel, burst_scan_kernel, fsm_scan_kernel, rate_scan_kernel) the scan frame: who
+// owns a key's run, the append of a transition, and when a wave walks on. The counter rates
+// (rate_scan_kernel) use the frame without the append: about one row leaves per element, placed
+// by arrival index and compacted in order (csrc/mxs_rate.h).
 // Included from .hip files only.
 //
 // The frame. The batch arrives stably sorted by key (`skeys`, with `perm` = the arrival index of

@@ -960,6 +960,109 @@ class StateMachineAlert(KeyedProcessFunction):
         self._state.update((since, to))
 
 
+class CounterRate(KeyedProcessFunction):
+    """The rate and the increase of a cumulative counter (Prometheus' ``irate()`` /
+    ``increase()``): interface octets, request totals and ``/proc/net/dev`` only mean something
+    as the difference between two consecutive samples of a key, and restart at zero with their
+    process. Per key the last accepted sample ``(ts, value[field])`` is kept; a key's first
+    element is only stored. An element with ``ts <= `` the stored one (a duplicate or a
+    straggler) is ignored and counted in ``out_of_order``. Any other element gives
+    ``dt = ts - last_ts``, ``inc = v - last if v >= last else v`` (a smaller reading is a counter
+    reset: the new reading is the increase) and becomes the stored sample; unless
+    ``dt > max_gap`` (the key is re-based silently) it collects
+    ``Tuple4(key, rate, inc, dt)`` with ``rate = float(inc) * per / dt``, `per` in
+    milliseconds, when there is no rule or ``rate <when> threshold`` holds. A key's counter is
+    all ints (Java longs: the subtraction wraps to 64 bits) or all floats (a NaN makes ``>=``
+    false, so ``inc = v``); `inc` is of the counter's kind. The comparison is Java's on two
+    doubles: a NaN is false for every operator but ``!=``. Output records carry their element's
+    timestamp; there are no timers. `per` is an int >= 1 (milliseconds) or a ``Time``, `max_gap`
+    None or such a duration below 2**62, `when` one of ``">", ">=", "<", "<=", "==", "!="`` and
+    given together with `threshold`. Bytes per second from raw interface counters, and the
+    hosts below 100 Mbit/s:
+
+        samples.key_by(0).process(CounterRate(2))
+        samples.key_by(0).process(CounterRate(2, per=Time.seconds(1), when="<",
+                                              threshold=100e6 / 8, max_gap=Time.minutes(2)))
+
+    The planner runs exactly this class (not a subclass) with a positional key on the device
+    operator (runtime/rate_operator.py); these methods are the exact host implementation used
+    otherwise."""
+
+    def __init__(self, field: int, per=1000, when=None, threshold=None, max_gap=None):
+        from .time import Time
+
+        if isinstance(field, bool) or not isinstance(field, int) or field < 0:
+            raise ValueError(f"CounterRate: field is a non-negative int, got {field!r}")
+        ms = per.to_milliseconds() if isinstance(per, Time) else per
+        if isinstance(ms, bool) or not isinstance(ms, int) or not 1 <= ms < 1 << 63:
+            raise ValueError("CounterRate: per is an int >= 1 (milliseconds) or a Time, "
+                             f"got {per!r}")
+        gap = max_gap.to_milliseconds() if isinstance(max_gap, Time) else max_gap
+        if gap is not None and (isinstance(gap, bool) or not isinstance(gap, int)
+                                or not 1 <= gap < 1 << 62):
+            raise ValueError("CounterRate: max_gap is None, an int >= 1 (milliseconds) or a "
+                             f"Time, below 2**62, got {max_gap!r}")
+        if when is None:
+            if threshold is not None:
+                raise ValueError("CounterRate: a threshold without when")
+        else:
+            if not isinstance(when, str) or when not in _LOOKUP_WHENS:
+                raise ValueError("CounterRate: when must be one of '>', '>=', '<', '<=', '==', "
+                                 f"'!=' or None, got {when!r}")
+            if threshold is None:
+                raise ValueError("CounterRate: when without a threshold")
+            self._number(threshold, "threshold")
+        self.field, self.per_ms, self.when, self.threshold = field, ms, when, threshold
+        self.max_gap_ms = gap
+        self.out_of_order = 0
+        self.native = ("counter_rate", field, ms, when, threshold, gap)
+
+    @staticmethod
+    def _number(x, what: str):
+        if isinstance(x, bool) or not isinstance(x, (int, float)):
+            raise TypeError(f"CounterRate: {what} must be an int or a float, got {x!r}")
+        if isinstance(x, int) and not -(1 << 63) <= x < 1 << 63:
+            raise TypeError(f"CounterRate: {what} is an int beyond 64 bits, got {x!r}")
+        return x
+
+    def open(self, parameters=None):
+        from .state import ValueStateDescriptor
+
+        self._state = self.get_runtime_context().get_state(ValueStateDescriptor("counter-rate"))
+
+    def process_element(self, value, ctx, out):
+        from .tuples import Tuple4
+
+        ts = ctx.timestamp()
+        if ts is None:
+            raise ValueError("CounterRate: a record without an event timestamp")
+        v = self._number(value[self.field], "the element's value")
+        cur = self._state.value()
+        if cur is None:
+            self._state.update((ts, v))
+            return
+        last_ts, last = cur
+        if isinstance(v, float) != isinstance(last, float):
+            raise TypeError("CounterRate: a key's counter is all ints or all floats, got "
+                            f"{v!r} after {last!r}")
+        if ts <= last_ts:
+            self.out_of_order += 1
+            return
+        dt = ts - last_ts
+        if v >= last:
+            inc = v - last
+            if isinstance(inc, int):
+                inc = (inc + (1 << 63)) % (1 << 64) - (1 << 63)  # Java's long subtraction
+        else:
+            inc = v
+        self._state.update((ts, v))
+        if self.max_gap_ms is not None and dt > self.max_gap_ms:
+            return
+        rate = float(inc) * float(self.per_ms) / float(dt)
+        if self.when is None or _LOOKUP_WHENS[self.when](rate, float(self.threshold)):
+            out.collect(Tuple4(ctx.get_current_key(), rate, inc, dt))
+
+
 class _NoTimerService:
     """What a function wrapped by EventTimeOrdered finds in place of the timer service."""
 
@@ -995,7 +1098,8 @@ class EventTimeOrdered(KeyedProcessFunction):
         samples.key_by(0).process(EventTimeOrdered(SustainedAlert(2, ">", 90.0, Time.minutes(5))))
 
     The planner runs exactly this class around exactly a ``SustainedAlert``, a ``BurstAlert``
-    (``times <= 16``) or a ``StateMachineAlert`` (at most 16 states) with a positional key on
+    (``times <= 16``), a ``StateMachineAlert`` (at most 16 states) or a ``CounterRate`` (whose
+    ``out_of_order`` then counts only equal timestamps) with a positional key on
     the device reorder buffer
     (runtime/reorder_operator.py) in front of the rule's device operator; these methods are the
     exact host implementation used otherwise."""

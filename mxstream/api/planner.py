@@ -29,7 +29,8 @@ BroadcastProcessOp.
 ``key_by(p).process(SustainedAlert(..))`` onto NativeSustainOp and
 ``key_by(p).process(BurstAlert(..))`` with ``times <= 16`` onto NativeBurstOp and
 ``key_by(p).process(StateMachineAlert(..))`` with at most 16 states onto NativeStateMachineOp
-(``_lower_keyed_process``), each of the last three also under ``EventTimeOrdered(..)``, with the
+and ``key_by(p).process(CounterRate(..))`` onto NativeCounterRateOp
+(``_lower_keyed_process``), each of the last four also under ``EventTimeOrdered(..)``, with the
 device reorder buffer in front; every other keyed process function keeps KeyedProcessOp.
 
 A ``window_all(..).process(WindowTopN(..))`` right behind such a window is folded into it
@@ -1010,18 +1011,19 @@ def _lower_keyed_process(env, t, meta) -> None:
     ``CountWithTimeout``, -> NativeSustainOp when it is exactly a ``SustainedAlert``, ->
     NativeBurstOp when it is exactly a ``BurstAlert`` with ``times <= 16``, the width of the
     engine's per-key ring, and -> NativeStateMachineOp when it is exactly a
-    ``StateMachineAlert`` with at most 16 states and 16 classes, what one packed function holds
+    ``StateMachineAlert`` with at most 16 states and 16 classes, what one packed function holds,
+    and -> NativeCounterRateOp when it is exactly a ``CounterRate``
     (not a subclass, whose methods may differ), the key is a field position and one rank runs
     the job. Every other keyed process function, a ``BurstAlert`` with more `times`, a
     ``StateMachineAlert`` with a larger table, key selectors and several ranks keep the host
     KeyedProcessOp.
 
     ``EventTimeOrdered(fn)`` (exactly that class) around exactly a ``SustainedAlert``, a
-    ``BurstAlert`` or a ``StateMachineAlert`` lowers, under the same conditions, onto the same
+    ``BurstAlert``, a ``StateMachineAlert`` or a ``CounterRate`` lowers, under the same conditions, onto the same
     operators with ``ordered=True``: the device reorder buffer in front of the rule."""
     from ..ops.kernels import BURST_MAX_TIMES, FSM_MAX_CLASSES, FSM_MAX_STATES
-    from ..runtime.native_ops import (NativeBurstOp, NativeStateMachineOp, NativeSustainOp,
-                                      NativeTimeoutOp)
+    from ..runtime.native_ops import (NativeBurstOp, NativeCounterRateOp, NativeStateMachineOp,
+                                      NativeSustainOp, NativeTimeoutOp)
     from . import functions as F
 
     fn, kp = meta["fn"], meta["key_pos"]
@@ -1032,11 +1034,12 @@ def _lower_keyed_process(env, t, meta) -> None:
         # the device reorder buffer in front of the rules; any other wrapped function keeps the
         # host wrapper
         fn, kw = fn.fn, {"ordered": True}
-        if type(fn) not in (F.SustainedAlert, F.BurstAlert, F.StateMachineAlert):
+        if type(fn) not in (F.SustainedAlert, F.BurstAlert, F.StateMachineAlert, F.CounterRate):
             return
     native = {F.CountWithTimeout: NativeTimeoutOp, F.SustainedAlert: NativeSustainOp,
               F.BurstAlert: NativeBurstOp,
-              F.StateMachineAlert: NativeStateMachineOp}.get(type(fn))
+              F.StateMachineAlert: NativeStateMachineOp,
+              F.CounterRate: NativeCounterRateOp}.get(type(fn))
     if native is None or kp is None or world > 1:
         return
     if native is NativeBurstOp and fn.times > BURST_MAX_TIMES:

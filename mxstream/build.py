@@ -28,10 +28,11 @@ HIP_SOURCES = ["kernels_hip.hip", "sort_hip.hip", "parse_hip.hip", "vector_hip.h
                "check_hip.hip", "rolling_hist_hip.hip", "ingest_hip.hip", "listwin_hip.hip",
                "format_hip.hip", "exchange_hip.hip", "join_hip.hip", "ijoin_hip.hip",
                "lookup_hip.hip", "timeout_hip.hip", "sustain_hip.hip",
-               "burst_hip.hip", "reorder_hip.hip", "ruleset_hip.hip", "fsm_hip.hip"]
+               "burst_hip.hip", "reorder_hip.hip", "ruleset_hip.hip", "fsm_hip.hip",
+               "rate_hip.hip"]
 CXX_SOURCES = ["kernels_cpu.cpp", "ingest_cpu.cpp", "runtime.cpp", "sessions.cpp", "vector_cpu.cpp",
                "vector_bindings.cpp", "trace.cpp", "check_cpu.cpp", "reader.cpp", "format.cpp", "listwin_cpu.cpp",
-               "listwin_bindings.cpp", "join_cpu.cpp", "join_bindings.cpp", "ijoin_cpu.cpp", "ijoin_bindings.cpp", "lookup_cpu.cpp", "lookup_bindings.cpp", "timeout_cpu.cpp", "timeout_bindings.cpp", "sustain_cpu.cpp", "sustain_bindings.cpp", "burst_cpu.cpp", "burst_bindings.cpp", "reorder_cpu.cpp", "reorder_bindings.cpp", "ruleset_cpu.cpp", "ruleset_bindings.cpp", "fsm_cpu.cpp", "fsm_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
+               "listwin_bindings.cpp", "join_cpu.cpp", "join_bindings.cpp", "ijoin_cpu.cpp", "ijoin_bindings.cpp", "lookup_cpu.cpp", "lookup_bindings.cpp", "timeout_cpu.cpp", "timeout_bindings.cpp", "sustain_cpu.cpp", "sustain_bindings.cpp", "burst_cpu.cpp", "burst_bindings.cpp", "reorder_cpu.cpp", "reorder_bindings.cpp", "ruleset_cpu.cpp", "ruleset_bindings.cpp", "fsm_cpu.cpp", "fsm_bindings.cpp", "rate_cpu.cpp", "rate_bindings.cpp", "window_tier_bindings.cpp", "window_control_bindings.cpp",
                "window_step.cpp", "window_step_bindings.cpp", "bindings.cpp"]
 # roctx ranges (csrc/trace.cpp) come from the ROCm profiler SDK's marker library.
 LINK_LIBS = ["-L/opt/rocm/lib", "-lrocprofiler-sdk-roctx", "-Wl,-rpath,/opt/rocm/lib"]
@@ -132,6 +133,7 @@ SANITIZE_PROGRAMS = {
     "reorder": ["reorder_cpu.cpp", "tests/sanitize_reorder_main.cpp"],
     "ruleset": ["ruleset_cpu.cpp", "tests/sanitize_ruleset_main.cpp"],
     "fsm": ["fsm_cpu.cpp", "tests/sanitize_fsm_main.cpp"],
+    "rate": ["rate_cpu.cpp", "tests/sanitize_rate_main.cpp"],
 }
 SANITIZE_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                   "-fno-sanitize-recover=all"]
@@ -161,7 +163,7 @@ def build_sanitize(verbose: bool = False) -> Path:
     return build_sanitize_program("", verbose)
 
 
-# build_sanitize_ijoin(verbose=False) .. build_sanitize_fsm: the names the tests import.
+# build_sanitize_ijoin(verbose=False) .. build_sanitize_rate: the names the tests import.
 for _name in filter(None, SANITIZE_PROGRAMS):
     globals()["build_sanitize_" + _name] = (
         lambda verbose=False, _n=_name: build_sanitize_program(_n, verbose))

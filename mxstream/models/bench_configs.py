@@ -1663,6 +1663,157 @@ def config21(steps: int, warmup: int, batch: int | None = None, keys: int = 1_00
             "device": str(dev)}
 
 
+def _rate_torch_step(table, keys, vals, ts, ts_base: int, span: int, per_ms: int, threshold):
+    """config 22's yardstick: the counter-rate step written with library ops on long counters --
+    stable sort by key, a segmented ``cummax`` of the timestamps (the segment number in the high
+    bits, so ``ts - ts_base`` must lie in [0, span)), gathers, the arithmetic, the rows put back
+    in arrival order and ``nonzero``. `table` is int64[keys, 2] = (last_ts, last value), last_ts
+    I64_MIN for a key never seen; it is updated. On a tie ``cummax`` keeps the later element, the
+    rule the earlier one: equal only where, as in config 22, a key's value is a function of its
+    timestamp. Returns the five columns."""
+    n = keys.numel()
+    sk, perm = torch.sort(keys, stable=True)
+    t, v = ts[perm], vals[perm]
+    head = torch.ones(n, dtype=torch.bool, device=keys.device)
+    head[1:] = sk[1:] != sk[:-1]
+    seg = torch.cumsum(head, 0) - 1
+    cm, at = torch.cummax(seg * span + (t - ts_base), 0)
+    carry = table[sk]
+    # exclusive: the element in front, unless this one begins its key's run
+    run_t = torch.roll(cm, 1) - seg * span + ts_base
+    run_v = v[torch.roll(at, 1)]
+    in_run = ~head & (run_t > carry[:, 0])
+    bt = torch.where(in_run, run_t, carry[:, 0])
+    bv = torch.where(in_run, run_v, carry[:, 1])
+    based = (t > bt) & (bt != K.I64_MIN)
+    inc = torch.where(v >= bv, v - bv, v)
+    dt = torch.where(based, t - bt, torch.ones_like(t))
+    rate = inc.to(torch.float64) * float(per_ms) / dt.to(torch.float64)
+    keep = based if threshold is None else based & (rate < threshold)
+    # the state: the run's arg-max against the carry, stored by the row that ends the run
+    tail = torch.ones(n, dtype=torch.bool, device=keys.device)
+    tail[:-1] = head[1:]
+    end_t = cm - seg * span + ts_base
+    newer = end_t > carry[:, 0]
+    rows = torch.stack([torch.where(newer, end_t, carry[:, 0]),
+                        torch.where(newer, v[at], carry[:, 1])], 1)
+    table[sk[tail]] = rows[tail]
+    # arrival order: scatter by the sort's permutation, then compact
+    mask = torch.zeros(n, dtype=torch.bool, device=keys.device)
+    mask[perm] = keep
+    cols = torch.empty((3, n), dtype=torch.int64, device=keys.device)
+    cols[0, perm] = rate.view(torch.int64)
+    cols[1, perm] = inc
+    cols[2, perm] = dt
+    idx = torch.nonzero(mask).squeeze(1)
+    return keys[idx], cols[0, idx], cols[1, idx], cols[2, idx], ts[idx]
+
+
+def config22(steps: int, warmup: int, batch: int | None = None, keys: int = 1_000_000,
+             threshold: float | None = None, zipf: float = 0.0, device: str = "cuda") -> dict:
+    """Counter rates at scale (``samples.key_by(0).process(CounterRate(2))``) on config 17's keys
+    and timestamps: `batch` device-generated samples per 1 s step (gen_events, uniform or zipf
+    keys) feed KeyedRateOperator directly. The value column is made on the device: key k's
+    counter grows with the timestamp at a slope of its own, 1000 .. 9999 per ms, and restarts
+    once every 1000 steps at a phase of its own, so about 0.1 % of the keys report a reset per
+    step. Without `threshold` every based sample is a row, the expansion-bound case; with one
+    the rule is ``rate < threshold`` (1 090 000 per second keeps the slowest 1 % of the keys).
+    The rows leave the device as five int64 columns (key id, rate bits, inc, dt, ts) in arrival
+    order.
+
+    Timed per step, each behind a device synchronise, alternating in the same call on the same
+    batch: the counter-rate step, config 17's native step (KeyedSustainOperator over a gauge
+    column of the same batch, ``for_`` = 3 s) and the torch composition of the same step
+    (_rate_torch_step). The ratios are reported, not gated. Outside the windows the C++ twin runs
+    every step on host copies: every step's row count and ignored samples, the first three
+    steps' rows and the final table must equal the device's, and the composition's row count
+    must equal them too. The sample generation is outside the windows."""
+    from ..runtime.rate_operator import KeyedRateOperator
+    from ..runtime.sustain_operator import KeyedSustainOperator
+
+    dev = torch.device(device)
+    batch = batch or (1 << 21)
+    when = None if threshold is None else "<"
+    op = KeyedRateOperator(1000, when, threshold, device=dev, dense_limit=max(keys, 1 << 26),
+                           capacity=keys)
+    sustain = KeyedSustainOperator(">", 90, 3_000, device=dev, dense_limit=max(keys, 1 << 26),
+                                   capacity=keys)
+    twin = K.rate_table(keys, "cpu")
+    lib = K.rate_table(keys, dev)
+    rule = dict(kind=K.SUSTAIN_LONG, per_ms=1000, when=when, threshold_bits=op.tbits,
+                max_gap=None)
+    step_ms = 1_000
+    t0_event = 1_566_957_600_000
+    sk, st, sv, gauge = (torch.empty(batch, dtype=torch.int64, device=dev) for _ in range(4))
+    state = {"i": 0}
+    rate_ms: list[float] = []
+    sustain_ms: list[float] = []
+    torch_ms: list[float] = []
+    ignored = {"native": 0, "twin": 0}
+
+    def step():
+        i = state["i"]
+        K.gen_events(sk, st, gauge, seed=17, stream_id=0, idx0=i * batch, nkeys=keys,
+                     ts_base=t0_event + i * step_ms, ts_span=step_ms, disorder=0, val_lo=0,
+                     val_span=100, zipf=zipf)
+        h = (sk + 1) * 2_654_435_761
+        slope = 1_000 + h % 9_000
+        since = i - (i - (h >> 7) % 1_000) % 1_000      # the key's last restart, a step number
+        sv.copy_(slope * (st - (t0_event + since * step_ms)))
+        _sync(dev)
+        t_in = time.perf_counter()
+        out = op.process(sk, sv, st, is_float=False)
+        _sync(dev)
+        rate_ms.append((time.perf_counter() - t_in) * 1e3)
+        t_in = time.perf_counter()
+        ref = sustain.process(sk, gauge, st, is_float=False)
+        _sync(dev)
+        sustain_ms.append((time.perf_counter() - t_in) * 1e3)
+        t_in = time.perf_counter()
+        comp = _rate_torch_step(lib, sk, sv, st, t0_event + i * step_ms, step_ms, 1000, threshold)
+        _sync(dev)
+        torch_ms.append((time.perf_counter() - t_in) * 1e3)
+        want, ooo = K.rate_update(twin, sk.cpu(), sv.cpu(), st.cpu(), **rule)
+        ignored["twin"] += ooo
+        rows = int(out[0][0].numel()) if out else 0
+        if rows != int(want[0].numel()) or (i < 3 and out and not all(
+                torch.equal(a.cpu(), b) for a, b in zip(out[0], want))):
+            raise RuntimeError("config 22: the native rows and the twin's differ")
+        if int(comp[0].numel()) != rows or (i < 3 and out and not all(
+                torch.equal(a, b) for a, b in zip(out[0], comp))):
+            raise RuntimeError("config 22: the torch composition's rows and the native ones differ")
+        state["i"] = i + 1
+        return rows, int(ref[0][0].numel()) if ref else 0
+
+    for _ in range(warmup):
+        step()
+    rate_ms.clear()
+    sustain_ms.clear()
+    torch_ms.clear()
+    rows = sustain_rows = 0
+    for _ in range(steps):
+        r, s = step()
+        rows, sustain_rows = rows + r, sustain_rows + s
+    if not torch.equal(op.state[:keys].cpu(), twin) or op.out_of_order != ignored["twin"]:
+        raise RuntimeError("config 22: the native table and the twin's differ")
+    if not torch.equal(lib.cpu(), twin):
+        raise RuntimeError("config 22: the torch composition's table and the twin's differ")
+    nat, ref, comp = _spread(rate_ms), _spread(sustain_ms), _spread(torch_ms)
+    return {"config": 22, "metric": "events/sec (counter rates: arg-max scan, dense rows)",
+            "value": batch / nat["median"] * 1e3, "unit": "events/s",
+            "ms_per_step": nat["median"], "native_ms": nat, "sustain_ms": ref, "torch_ms": comp,
+            "sustain_events_per_s": batch / ref["median"] * 1e3,
+            "rate_over_sustain_time": nat["median"] / ref["median"],
+            "torch_over_rate_time": comp["median"] / nat["median"],
+            "rows": rows, "rows_per_step": rows // max(1, steps),
+            "row_share": rows / max(1, steps * batch),
+            "sustain_rows_per_step": sustain_rows // max(1, steps),
+            "out_of_order": op.out_of_order,
+            "keys_seen": int((twin[:, 0] != K.RATE_NONE).sum()),
+            "threshold": threshold, "keys": keys, "samples_per_step": batch, "zipf": zipf,
+            "table_rows": op.cap, "steps": steps, "warmup": warmup, "device": str(dev)}
+
+
 def bandwidth_text(lines: int, channels: int = 1_000, seed: int = 7) -> np.ndarray:
     """Synthetic chapter3 input (chapter3/README.md:286 format, ``BandwidthMonitorWithEventTime``)
     as fixed-width lines ``yyyy-MM-ddTHH:mm:ss chNNN.example.com VVVVVVVVV`` over one hour of
@@ -1945,7 +2096,7 @@ def config10(steps: int, warmup: int, batch: int = 1 << 24, keys: int = 1_000_00
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21])
+    ap.add_argument("--config", type=int, required=True, choices=[1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22])
     ap.add_argument("--top-n", type=int, nargs="?", const=10, default=None,
                     help="config 10: cut every firing to its top N on the device (default N = "
                          "10); without it the firing leaves in full and numpy takes the top 10")
@@ -1965,8 +2116,13 @@ def main(argv=None) -> int:
                     help="config 5: fraction of events for spilled (long idle) keys")
     ap.add_argument("--lo", type=int, default=-500, help="config 14: lower bound in ms")
     ap.add_argument("--hi", type=int, default=500, help="config 14: upper bound in ms")
-    ap.add_argument("--when", choices=["gt", "none"], default="gt",
-                    help="config 15: sample > threshold (about 1 %% kept) or keep every sample")
+    ap.add_argument("--when", choices=["gt", "none", "<"], default="gt",
+                    help="config 15: sample > threshold (about 1 %% kept) or keep every sample; "
+                         "config 22: '<' adds the rule rate < --threshold (otherwise every based "
+                         "sample is a row)")
+    ap.add_argument("--threshold", type=float, default=1_090_000.0,
+                    help="config 22 with --when '<': the rate per second below which a sample "
+                         "leaves (the default keeps the slowest 1 %% of the keys)")
     ap.add_argument("--timeout-ms", type=int, default=3_000,
                     help="config 16: a key fires after this much silence (event time)")
     ap.add_argument("--for-ms", type=int, default=3_000,
@@ -2083,6 +2239,10 @@ def main(argv=None) -> int:
     elif a.config == 21:
         r = config21(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000, states=a.states,
                      zipf=a.zipf, device=a.device)
+    elif a.config == 22:
+        r = config22(a.steps, a.warmup, a.batch, keys=a.keys or 1_000_000,
+                     threshold=a.threshold if a.when == "<" else None, zipf=a.zipf,
+                     device=a.device)
     elif a.config == 6:
         r = config6(a.steps, a.warmup, a.batch or (1 << 24), dim=a.dim, device=a.device,
                     mfma=not a.valu, zipf=a.zipf)

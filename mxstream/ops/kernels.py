@@ -1552,6 +1552,99 @@ def fsm_update(state: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, ts: 
         code_bits=FSM_TAG_BITS, gather="gpu_fsm_gather")
 
 
+# ---- counter rates (csrc/mxs_rate.h) ------------------------------------------------------------
+
+RATE_NONE = I64_MIN           # last_ts of a key that was never seen
+
+
+def rate_table(cap: int, device) -> torch.Tensor:
+    """Fresh state for `cap` key ids: int64[cap, 2], every row (RATE_NONE, 0)."""
+    if cap < 1:
+        raise ValueError("rate: cap must be >= 1")
+    state = torch.zeros((cap, 2), dtype=torch.int64, device=device)
+    state[:, 0] = RATE_NONE
+    return state
+
+
+def rate_update(state: torch.Tensor, keys: torch.Tensor, vals: torch.Tensor, ts: torch.Tensor,
+                *, kind: int, per_ms: int, when, threshold_bits: int, max_gap,
+                bounds: tuple | None = None):
+    """A batch of counter readings in arrival order (key ids, value bits of `kind`, timestamps):
+    an element whose timestamp is above its key's last accepted one is accepted, becomes the
+    key's row, and, when the key had a row, gives ``dt``, ``inc`` (``v - last``, or ``v`` after
+    a restart) and ``rate = float(inc) * per_ms / dt``; the row leaves when ``dt <= max_gap``
+    (`max_gap` None: always) and ``rate <when> threshold`` holds (`when` None: always). Every
+    other element of a key that has a row is ignored and counted. Returns ``(five int64 columns
+    in arrival order (key id, rate bits, inc bits, dt, ts), ignored elements)``. Every key must
+    lie in [0, cap) and every timestamp strictly inside (-2**62, 2**62) (`bounds` = (largest
+    key, smallest and largest timestamp) when the caller has read them, else one readback). GPU:
+    stable radix sort by key, one segmented wave scan that places (inc, dt) by arrival index, a
+    mask over tiles, their scan, the counts' readback (the only one) and the emit in arrival
+    order: no second sort. A one-row batch skips the sort."""
+    dev = state.device
+    try:
+        cap = _lookup_table(state)
+    except ValueError:
+        raise ValueError("rate_update: the table must be a contiguous, 16-byte aligned int64 "
+                         "[cap, 2] tensor with cap >= 1") from None
+    n = _lookup_cols((keys, vals, ts), ("keys", "vals", "ts"), dev)
+    code = lookup_when(when)
+    if kind not in (SUSTAIN_LONG, SUSTAIN_DOUBLE):
+        raise ValueError("rate_update: kind must be SUSTAIN_LONG or SUSTAIN_DOUBLE")
+    if not _is_int(per_ms) or not 1 <= per_ms <= I64_MAX:
+        raise ValueError("rate_update: per_ms must be a positive int64")
+    if max_gap is not None and (not _is_int(max_gap) or not 1 <= max_gap < SUSTAIN_TS_LIMIT):
+        raise ValueError("rate_update: max_gap must be None or an int in [1, 2**62)")
+    tbits = int(threshold_bits)
+    if not I64_MIN <= tbits <= I64_MAX:
+        raise ValueError("rate_update: threshold_bits must be an int64 bit pattern")
+    if n >= 1 << 31:
+        raise ValueError("rate_update: at most 2**31 - 1 rows per batch")
+    out = torch.empty((5, n), dtype=torch.int64, device=dev)
+    if n == 0:
+        return tuple(out[c] for c in range(5)), 0
+    cuda = _is_gpu(state)
+    if bounds is None or not cuda:
+        lo, hi, tmin, tmax = torch.stack([keys.min(), keys.max(), ts.min(), ts.max()]).tolist()
+    else:
+        lo, (hi, tmin, tmax) = 0, (int(b) for b in bounds)
+    if lo < 0 or hi >= cap:
+        raise ValueError(f"rate_update: keys must lie in [0, {cap})")
+    if tmin <= -SUSTAIN_TS_LIMIT or tmax >= SUSTAIN_TS_LIMIT:
+        raise TypeError("rate_update: a timestamp at or beyond 2**62")
+    m = load()
+    rule = (kind, code, tbits, per_ms, max_gap or 0)
+    if not cuda:
+        rows, ignored = m.cpu_rate_update(_p(keys), _p(vals), _p(ts), n, *rule, _p(state), cap,
+                                          *(_p(out[c]) for c in range(5)))
+        return tuple(out[c, :rows] for c in range(5)), ignored
+    st = _stream(state)
+    if n == 1:
+        skeys, perm = keys, torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        skeys, perm = sort_pairs(keys, idx, bits=max(1, hi.bit_length()))
+    ntiles = (n + m.LOOKUP_TILE - 1) // m.LOOKUP_TILE
+    scratch = torch.empty((n, 2), dtype=torch.int64, device=dev)   # (inc bits, dt) by arrival
+    words = torch.empty(ntiles * m.LOOKUP_WORDS, dtype=torch.int64, device=dev)
+    counts = torch.empty(ntiles, dtype=torch.int32, device=dev)
+    offsets = torch.empty(ntiles, dtype=torch.int64, device=dev)
+    # [rows, unused (lookup_scan's), ignored elements (a uint32 in the low half)]
+    meta = torch.zeros(m.LOOKUP_META + 1, dtype=torch.int64, device=dev)
+    m.gpu_rate_scan(_p(skeys), _p(perm), _p(vals), _p(ts), n, kind, _p(state), cap, _p(scratch),
+                    _p(meta) + 8 * m.LOOKUP_META, st)
+    m.gpu_rate_mask(_p(scratch), n, *rule, _p(words), _p(counts), st)
+    m.lookup_scan(True, _p(counts), ntiles, _p(offsets), _p(meta), st)
+    got = meta.tolist()  # the only readback
+    rows, ignored = got[0], got[m.LOOKUP_META]
+    if not 0 <= rows <= n or not 0 <= ignored <= n:
+        raise RuntimeError("rate_update: more rows than elements")
+    if rows:
+        m.gpu_rate_emit(_p(scratch), _p(keys), _p(ts), n, *rule, _p(words), _p(counts),
+                        _p(offsets), rows, *(_p(out[c]) for c in range(5)), st)
+    return tuple(out[c, :rows] for c in range(5)), ignored
+
+
 # ---- event-time reorder buffer (csrc/mxs_reorder.h) ---------------------------------------------
 
 REORDER_TILE = 4096           # output positions a workgroup of the collect owns

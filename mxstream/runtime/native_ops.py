@@ -2926,6 +2926,50 @@ class NativeStateMachineOp(NativeSustainOp):
                            self.dict if self.str_keys else None, t, self._subtasks(key), False)
 
 
+class NativeCounterRateOp(NativeSustainOp):
+    """``stream.key_by(p).process(CounterRate(field, per, when, threshold, max_gap))`` on the
+    device operator (runtime/rate_operator.py; planner._lower_keyed_process). Inputs, buffering,
+    event-time order, what counts as unsupported data and what becomes of it are
+    NativeSustainOp's; the engine, the checkpoint's key ("counter_rate") and the output differ:
+    one host ColumnBatch ``(key, rate, inc, dt)`` with the samples' timestamps, in arrival
+    order, `inc` of the counter's kind. ``out_of_order`` is the engine's count of ignored
+    samples."""
+
+    name = "KeyedProcess(native counter rate)"
+    fn_name, snap_key, snap_what = "CounterRate", "counter_rate", "counter-rate"
+
+    def _rule(self, fn) -> None:
+        self.per_ms, self.when, self.threshold = fn.per_ms, fn.when, fn.threshold
+        self.max_gap_ms = fn.max_gap_ms
+
+    def _build(self) -> None:
+        from .rate_operator import KeyedRateOperator
+
+        self.op = KeyedRateOperator(self.per_ms, self.when, self.threshold, self.max_gap_ms,
+                                    device=torch.device(self.device),
+                                    dense_limit=self.dense_limit)
+
+    @property
+    def out_of_order(self) -> int:
+        return self.op.out_of_order if self.op is not None else 0
+
+    def _rule_rows(self, keys, bits, ts) -> list:
+        if self.op is None:
+            self._build()
+        out = []
+        is_float = self.is_float[0]
+        for cols in self.op.process(keys, bits, ts, is_float=is_float):
+            key, rate, inc, dt, t = (np.ascontiguousarray(c.cpu().numpy()) for c in cols)
+            out.append(ColumnBatch(int(key.size),
+                                   [key, rate.view(np.float64),
+                                    inc.view(np.float64) if is_float else inc, dt],
+                                   (FK_STR if self.str_keys else FK_LONG, FK_DOUBLE,
+                                    FK_DOUBLE if is_float else FK_LONG, FK_LONG),
+                                   self.dict if self.str_keys else None, t,
+                                   self._subtasks(key), False))
+        return out
+
+
 def _same_spec(a, b) -> bool:
     """Function parameters equal, a NaN default equal to itself, 1 and 1.0 apart."""
     return len(a) == len(b) and all(
